@@ -8,10 +8,12 @@ global-norm clip + Adam + teacher EMA (+ one RCCL all-reduce of the grads for N 
 Post-warm-up epoch 60 (full loss weights) with a confident synthetic teacher, so the KL and
 ECDA terms are active.  Inputs are resident in HBM before timing.
 Order of a run: ~50 ms of untimed headline steps to settle the clocks (--settle-ms, `settle_steps` in
-the line), the W warm-up steps, the K timed steps, a per-kernel pass, the parity block, then the side
-legs (FP32 / BF16 modes, random labels, data path) and the CPU baseline.
+the line), the W warm-up steps, the K timed steps, then (--dump-outputs DIR) the last timed step's
+outputs written as DIR/<name>.npy, and the result line.  With --full the run goes on after the timed
+steps: a per-kernel pass, the parity block, then the side legs (FP32 / BF16 modes, random labels,
+data path) and the CPU baseline, all reported in the same line.
 
-    python bench.py [--gpus N --steps K --warmup W --precision fp16|bf16|fp32]
+    python bench.py [--gpus N --steps K --warmup W --precision fp16|bf16|fp32] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...          (one process per GPU)
 
 Prints ONE JSON line (rank 0).
@@ -375,7 +377,7 @@ def mixed_fold_train(starts, meta, k):
     return np.concatenate([s + t for s, t in zip(starts, tr)])
 
 
-def run_mixed(args, model, dev, rank, world, dist, comm):
+def run_mixed(args, model, dev, rank, world, dist, comm, after_timed=None):
     """BASELINE configs[4]: mixed IEMOCAP+CASIA+EMODB batches, K-fold throughput sweep.  Every
     step's clean and noisy batches mix utterances of the three corpora (fused store-mode
     loaders over the unions of the fold's training splits, variable lengths); the DAD config
@@ -438,7 +440,9 @@ def run_mixed(args, model, dev, rank, world, dist, comm):
             utts = int(u.item())
         folds.append({"fold": k, "train_utterances": int(len(tr)), "seconds": el, "utterances": utts,
                       "value": utts / el, "avg_valid_frames_per_step": rows / args.steps})
-    table = kernel_pass(lambda: run(1, False), args.kernel_steps)
+    if after_timed is not None:
+        after_timed(step)
+    table = kernel_pass(lambda: run(1, False), args.kernel_steps) if args.full else {}
     return step, folds, merge_ktimes(ktimes), table
 
 
@@ -672,14 +676,15 @@ def rooflines(ktimes, rows_c, rows_n, ms_step, precision, tail_name="dad_tail_ec
         srf["step_traffic_stale"] = tr["stale"]
     # MFMA utilisation of the encoder linears (north_star: >= 40 %): algorithmic FLOPs / time / peak
     enc_tf = enc_flops / (enc * 1e-3) / 1e12
-    wg_tf = wg_flops / (wg * 1e-3) / 1e12
     mf = {ekn: {"flops": enc_flops, "avg_ms": enc, "tflops": enc_tf, "util": enc_tf / peak_tf},
-          wname: {"flops": wg_flops, "avg_ms": wg, "tflops": wg_tf, "util": wg_tf / peak_tf},
-          "encoder_linears": {"flops": enc_flops + wg_flops, "ms": enc + wg,
-                              "util": (enc_flops + wg_flops) / ((enc + wg) * 1e-3) / 1e12 / peak_tf,
-                              "target": MFMA_TARGET},
           "peak_tflops": peak_tf, "peak_source": "MI355X_MICROARCH.md dense MFMA peak (%s)" % precision}
-    for kn in (ekn, wname):   # matrix-pipe busy share from the committed PMC pass, when it covers this library
+    if wkey in ktimes:        # (a run that timed the encoder only has no weight-gradient time: no entries, not NaN)
+        wg_tf = wg_flops / (wg * 1e-3) / 1e12
+        mf[wname] = {"flops": wg_flops, "avg_ms": wg, "tflops": wg_tf, "util": wg_tf / peak_tf}
+        mf["encoder_linears"] = {"flops": enc_flops + wg_flops, "ms": enc + wg,
+                                 "util": (enc_flops + wg_flops) / ((enc + wg) * 1e-3) / 1e12 / peak_tf,
+                                 "target": MFMA_TARGET}
+    for kn in (k for k in (ekn, wname) if k in mf):   # matrix-pipe busy share from the committed PMC pass, when it covers this library
         pk = pmc_counters(kn)
         if pk and pk.get("mfma_busy_frac") is not None:
             mf[kn]["pmc_matrix_busy_frac"] = pk["mfma_busy_frac"]
@@ -688,6 +693,44 @@ def rooflines(ktimes, rows_c, rows_n, ms_step, precision, tail_name="dad_tail_ec
     kern["encoder_roofline"] = enc_rf
     kern["launch_rooflines"] = launch_rf
     return rf, srf, kern
+
+
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs writes at most this much (about 4 MB at the default batch)
+
+
+def last_step_outputs(model, step):
+    """What a caller of the timed path holds after its last step, as float32 host arrays: the loss
+    terms DADStep.step() returns, the step's per-utterance outputs (DADStep.outputs(): embeddings,
+    logits, DACP scores / predictions / mask / class probabilities, thresholds, the gradient
+    and its clip norm) and the state the step updated (student and teacher parameters, Adam
+    moments, DACP state).  Host copies: later steps do not change them."""
+    out = {k: v for k, v in step.losses().items()}
+    o = step.outputs(*step._last_shape)
+    for k in ("e_clean", "e_teacher", "e_strong", "z_clean", "z_teacher", "z_strong", "score", "pred", "mask", "q",
+              "w", "tau_before", "tau_after", "ecda_terms", "clip_norm", "clip_coef", "msum", "ecda_on", "grad"):
+        out[k] = o[k]
+    out.update(student_params=model.student_flat, teacher_params=model.teacher_flat, exp_avg=step.exp_avg,
+               exp_avg_sq=step.exp_avg_sq, dacp=step.dacp)
+    torch.cuda.synchronize()
+    return {k: np.atleast_1d(v.detach().to(torch.float32).cpu().numpy()) for k, v in out.items()}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one <name>.npy (float32) per array of last_step_outputs(); returns the shapes
+    written.  Past DUMP_LIMIT_BYTES in all (a very large --batch), every array above an equal share
+    of the limit is written as a fixed sample of its elements: the same seeded, sorted indices into
+    the flattened array in every run."""
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    sample = sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for k, a in sorted(arrays.items()):
+        if sample and a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+        shapes[k] = list(a.shape)
+    return shapes
 
 
 def snapshot(model, step):
@@ -853,8 +896,23 @@ def main():
     ap.add_argument("--launch", default="eager", choices=["graph", "eager"],
                     help="timed steps as eager launches (default) or hipGraph replays (one graph per resident batch; "
                          "measured no faster on this ROCm, DESIGN.md §5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (losses, per-utterance "
+                         "outputs, updated parameters and state) as DIR/<name>.npy in float32; the inputs are seeded, "
+                         "so two runs with the same arguments can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel pass, the parity block, the side legs (FP32 / "
+                         "BF16 modes, random labels, data path) and the CPU baseline (each with its own switch above); "
+                         "without it the run ends with the timed steps")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     settle_steps = 0
+    dumped = {}
+
+    def capture(s):          # written right after the timed steps, before anything else runs a step
+        if args.dump_outputs and rank == 0:
+            dumped.update(dump_outputs(args.dump_outputs, last_step_outputs(model, s)))
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -893,7 +951,7 @@ def main():
         sys.exit(3)
     folds = None
     if args.mixed:
-        step, folds, ktimes, table = run_mixed(args, model, dev, rank, world, dist, comm)
+        step, folds, ktimes, table = run_mixed(args, model, dev, rank, world, dist, comm, after_timed=capture)
         elapsed = sum(f["seconds"] for f in folds)
         total_utts = sum(f["utterances"] for f in folds)
         timed_steps = args.steps * args.folds
@@ -935,7 +993,7 @@ def main():
         # us per step over consecutive 20-step segments), the timed region, then the per-kernel pass,
         # the parity block (from the state the region started in) and the side legs.
         parity = fp32 = bf16 = data_path = randlab = None
-        side = rank == 0 and world == 1
+        side = args.full and rank == 0 and world == 1
         launch = args.launch
         if launch == "graph" and isinstance(comm, PKG.ProcessGroupComm):
             launch = "eager (the gloo all-reduce runs on the host: not capturable)"
@@ -1032,7 +1090,8 @@ def main():
         nbc = step._last_shape
         msum = float(step.outputs(*nbc)["msum"])
         ecda_on = float(step.outputs(*nbc)["ecda_on"])
-        table = kernel_pass(lambda: run(1), args.kernel_steps)
+        capture(step)
+        table = kernel_pass(lambda: run(1), args.kernel_steps) if args.full else {}
         if side and args.precision != "fp32" and not args.no_parity:
             parity = parity_block(model, step, view, snap, data[args.warmup % len(data)], args.epoch,
                                   args.precision)
@@ -1107,8 +1166,11 @@ def main():
         src = "%s: HIP events around them in the timed region (every %d-th step)" % (
             ", ".join({"wgrad": "weight gradient (+ clean-row conversion)", "tail": "tail launch (+ pooling, noisy-row "
                        "preparation)", "encode": "encoder"}[k] for k in tks), event_every(args.steps))
-    kern["source"] = ("%s; the other kernels: a separate eager pass of %d steps after it (events at every "
-                      "boundary of every 2nd step)" % (src, args.kernel_steps))
+    if args.full:
+        kern["source"] = ("%s; the other kernels: a separate eager pass of %d steps after it (events at every "
+                          "boundary of every 2nd step)" % (src, args.kernel_steps))
+    else:
+        kern["source"] = "%s; the other kernels are timed only with --full" % src
     line = {
         "metric": METRIC, "value": value, "unit": "utterances/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "settle_steps": settle_steps, "ms_per_step": ms, "higher_is_better": True,
@@ -1141,7 +1203,9 @@ def main():
         line["random_labels"] = randlab
     if data_path is not None:
         line["data_path"] = data_path
-    if world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:
+        line["dumped_outputs"] = dumped
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(B, T, args.cpu_steps, args.epoch)
     print(json.dumps(line), flush=True)
     if comm is not None:

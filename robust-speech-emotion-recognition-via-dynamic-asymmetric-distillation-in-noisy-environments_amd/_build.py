@@ -1,7 +1,10 @@
 """Build libdad_hip.so (the C-ABI library of include/dad.h) in-tree for gfx950.
 
 Plain `hipcc --offload-arch=gfx950` per translation unit + one shared-library link; the
-result lands in <package>/lib/ so it travels with the repo snapshot to the GPU box.
+result (and every variant library, lib_path()) lands in lib/ at the top of the repository, not
+inside the package: the package folder's name alone is 104 characters, which inside it puts the
+library's absolute path past 255 characters in any checkout whose own path has 134 or more, and
+a record of a process's mapped libraries that holds 255 characters per path then loses it.
 """
 import concurrent.futures
 import os
@@ -10,7 +13,7 @@ import sys
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
-LIB_DIR = os.path.join(PKG_DIR, "lib")
+LIB_DIR = os.path.join(os.path.dirname(PKG_DIR), "lib")
 OBJ_DIR = os.path.join(PKG_DIR, "build")
 LIB_PATH = os.path.join(LIB_DIR, "libdad_hip.so")
 SOURCES = ["encode.hip", "encode_ws.hip", "tail.hip", "wgrad.hip", "optim.hip", "dad_abi.hip", "rccl_dp.hip", "collate.hip", "eval.hip", "utils_abi.hip", "prep.hip"]

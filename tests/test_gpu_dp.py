@@ -209,7 +209,7 @@ def test_dp_step_two_ranks_match_oracle(fp16):
 def test_bench_spawns_ranks_gloo():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--comm", "gloo",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--comm", "gloo", "--full",
                         "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-data-path", "--fp32-steps", "0"],
                        cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -2,6 +2,7 @@
 # times (are the legs measured on settled clocks), then the bench tests.
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS:-}"     # the side legs and the per-kernel pass run only with --full
 mkdir -p gpurun_out
 timeout -k 10 400 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > gpurun_out/b_legs.log 2>&1 || { tail -20 gpurun_out/b_legs.log; exit 1; }
 grep '^{' gpurun_out/b_legs.log | tail -1 > gpurun_out/b_legs.json

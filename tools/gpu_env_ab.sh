@@ -7,7 +7,7 @@ mkdir -p gpurun_out/ab
 for r in $(seq 1 ${AB_ROUNDS:-3}); do
   for v in default switched; do
     if [ "$v" = default ]; then e=""; else e="${AB_ENV}"; fi
-    env $e timeout -k 10 200 python bench.py --no-cpu-baseline --no-parity --fp32-steps 0 --bf16-steps 0 --randlab-steps 0 --no-data-path \
+    env $e timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-parity --fp32-steps 0 --bf16-steps 0 --randlab-steps 0 --no-data-path \
       --steps ${AB_STEPS:-300} ${BENCH_ARGS:-} > gpurun_out/ab/env_$v.$r.log 2>&1 || { echo "FAIL $v"; tail -5 gpurun_out/ab/env_$v.$r.log; exit 1; }
     python -c "
 import json; d=json.loads([l for l in open('gpurun_out/ab/env_$v.$r.log') if l.startswith('{')][-1])

@@ -4,13 +4,14 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 R="$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out/pmc32
+O=$R/${PROFILE_OUT:-bench_out}/pmc32      # one folder per pass, under the output folder tools/gpu_full.sh also uses
+mkdir -p "$O"
 cd /tmp
 pass() {
   name=$1; shift
   timeout -s KILL 240 rocprofv3 --pmc "$@" --kernel-trace --kernel-include-regex "${PMC_REGEX:-dad_(encode|wgrad)_f32|dad_wsum}" --output-format csv \
-    -d "$R/gpurun_out/pmc32/$name" -o run -- python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-parity --fp32-steps 6 --bf16-steps 0 --no-data-path \
-    > "$R/gpurun_out/pmc32/$name.log" 2>&1 && python "$R/tools/pmc_brief.py" "$R/gpurun_out/pmc32/$name/run_counter_collection.csv"
+    -d "$O/$name" -o run -- python "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-parity --fp32-steps 6 --bf16-steps 0 --no-data-path \
+    > "$O/$name.log" 2>&1 && python "$R/tools/pmc_brief.py" "$O/$name/run_counter_collection.csv"
 }
 if [ -n "${PMC_SETS:-}" ]; then
   # PMC_SETS="A B C;D E" -> one pass per ';'-separated set

@@ -2,6 +2,7 @@
 # (the driver's flags) and --steps 200 --warmup 50, alternating, all side legs on (no CPU baseline).
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS:-}"     # the side legs and the per-kernel pass run only with --full
 mkdir -p gpurun_out/region
 for r in 1 2; do
   for s in "20 5" "200 50"; do

@@ -12,6 +12,7 @@ grep -E "passed|failed|error" gpurun_out/pytest_gpu.log | tail -3
 grep -E "^FAILED|^ERROR" gpurun_out/pytest_gpu.log | head -20
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest rc $rc: stopping"; exit $rc; fi
 if [ -n "${NO_BENCH:-}" ]; then exit $rc; fi
+BENCH_ARGS="--full ${BENCH_ARGS:-}"     # the default line with every leg and the CPU baseline
 timeout -k 10 ${BENCH_LIMIT:-400} python -u bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1
 brc=$?
 grep '^{' gpurun_out/bench.log | tail -1 > gpurun_out/bench.json

@@ -63,9 +63,7 @@ N_SIMDS = 1024   # MI355X: 256 CUs x 4 SIMDs
 
 def lib_sha16():
     import hashlib
-    p = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                     "robust-speech-emotion-recognition-via-dynamic-asymmetric-distillation-in-noisy-environments_amd",
-                     "lib", "libdad_hip.so")
+    p = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "libdad_hip.so")
     try:
         return hashlib.sha256(open(p, "rb").read()).hexdigest()[:16]
     except OSError:
