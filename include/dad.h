@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DAD_ABI_VERSION 7
+#define DAD_ABI_VERSION 8
 
 /* error codes (besides hipError_t values) */
 #define DAD_OK 0
@@ -172,7 +172,7 @@ typedef struct dad_state {
 } dad_state;
 
 /* --- sizing ------------------------------------------------------------------------ */
-/* DAD_ABI_VERSION the library was built with (ABI 7; 6 lacked dad_timing_reset): a binding compares it with the header's
+/* DAD_ABI_VERSION the library was built with (ABI 8; 7 lacked dad_eval_split, 6 dad_timing_reset): a binding compares it with the header's
  * value when it loads the library, so a stale build fails at load instead of at a call. */
 int dad_abi_version(void);
 size_t dad_param_count(void);
@@ -314,6 +314,70 @@ int dad_collate_index_epoch(const int64_t* offsets, const int32_t* sizes, int64_
  * max_prob * (1 - H/log2 C) or max_prob) and the argmax pred [B].  Outputs may be NULL. */
 int dad_predict_head(const float* e, int B, const float* w2, const float* b2, int use_entropy,
                      float* logits, float* probs, float* score, int64_t* pred, void* stream);
+
+/* --- whole-split evaluation, store-fed (csrc/eval_split.hip; ABI 8) ---------------------
+ * Trainer.validate (I/train.py:522-564), the teacher pass of its disagreement rate,
+ * Trainer._run_anchor_calibration's statistics (I/train.py:317-357) and the split-wide
+ * SSRLModel.get_embeddings (I/model.py:247-265) over EVERY utterance of a feature-store split in
+ * one call: the eval-mode forward reads the store rows in place (no padded batch, no mask) and
+ * the confusion matrices, the teacher disagreement count and the per-class certainty moments are
+ * built on the device.  The caller copies one small result block back.
+ *
+ * Result block: counts[DAD_EV_COUNTS] int64 and moments[4][DAD_EV_MOMENTS] double. */
+#define DAD_EV_CONF_STUDENT 0   /* [4][4] row = label, column = student prediction (labelled utterances) */
+#define DAD_EV_CONF_TEACHER 16  /* [4][4] the same for the teacher (zeros without one) */
+#define DAD_EV_DISAGREE 32      /* student pred != teacher pred, over all n utterances (0 without a teacher) */
+#define DAD_EV_N 33             /* n */
+#define DAD_EV_N_LABELLED 34    /* utterances with a label in [0, 4) */
+#define DAD_EV_N_SKIPPED 35     /* label outside [0, 4), or labels == NULL (then n) */
+#define DAD_EV_N_NONFINITE 36   /* utterances with a student or teacher logit that is not finite (FP16: an
+                                   operand beyond +-65504; any mode: non-finite features) */
+#define DAD_EV_COUNTS 40        /* int64 slots of the counts block (37..39 reserved, written 0) */
+/* moments[c][.] of the student's certainty score over the utterances of true class c, in float64
+ * over the float32 scores, two passes in a fixed order (np.mean / np.std ** 2 of the reference's
+ * .item() lists); count 0 gives mean = variance = 0 */
+#define DAD_EV_MOMENTS 3
+#define DAD_EV_M_COUNT 0
+#define DAD_EV_M_MEAN 1
+#define DAD_EV_M_VAR 2          /* population variance */
+/* Utterance i < n is frames [rows[i], rows[i] + lens[i]) of the store (rows need be neither sorted
+ * nor unique; lens[i] = 0 reads nothing and gives a zero embedding, logits = b2).  The slab jobs are
+ * described by the device prefix slab_off[n + 1] (int32): slab_off[0] = 0, slab_off[i + 1] =
+ * slab_off[i] + ceil(lens[i] / 32); `slabs` is its last entry, on the host.  An utterance whose
+ * prefix entries disagree with its length gets a zero embedding (nothing is read for it).
+ * Per-utterance outputs are optional (NULL = not written).  Two calls on the same inputs write
+ * bit-identical outputs (no floating-point atomics). */
+typedef struct dad_eval_args {
+  const void* store;            /* [frames][768], dtype store_dtype */
+  const int64_t* rows;          /* [n] store row of frame 0 */
+  const int32_t* lens;          /* [n] frames */
+  const int64_t* labels;        /* [n] or NULL */
+  const int32_t* slab_off;      /* [n + 1] exclusive prefix of ceil(lens / 32) */
+  const float* student;         /* [DAD_NPARAM] flat [W1|b1|W2|b2] */
+  const float* teacher;         /* [DAD_NPARAM] or NULL: no teacher pass */
+  float* emb;                   /* [n][256] student embeddings */
+  float* logits;                /* [n][4] */
+  float* probs;                 /* [n][4] */
+  float* score;                 /* [n] certainty score (dad_predict_head's) */
+  int64_t* pred;                /* [n] first-maximum argmax */
+  float* t_emb;                 /* [n][256] teacher */
+  float* t_logits;              /* [n][4] */
+  int64_t* t_pred;              /* [n] */
+  int64_t* counts;              /* [DAD_EV_COUNTS] */
+  double* moments;              /* [4][DAD_EV_MOMENTS] */
+  int64_t n;                    /* utterances, >= 1 */
+  int64_t slabs;                /* slab_off[n] */
+  int32_t store_dtype;          /* DAD_STORE_* */
+  int32_t use_entropy;          /* USE_ENTROPY_IN_SCORE */
+  int32_t precision;            /* DAD_PREC_FP32 (exact-f32 MFMA, the reference's eval arithmetic) or
+                                   DAD_PREC_FP16 (rows and W1 rounded to fp16, fp32 accumulation) */
+  int32_t reserved;
+} dad_eval_args;
+/* workspace bytes of dad_eval_split (0 for an unsupported n / slabs); no initialisation needed */
+size_t dad_eval_workspace_bytes(int64_t n, int64_t slabs, int precision, int with_teacher);
+/* DAD_E_ARG: a required pointer is NULL or a dtype / precision value is unknown; DAD_E_SHAPE: n < 1 or
+ * slabs outside [0, n * 2^26]; DAD_E_UNSUPPORTED: DAD_PREC_BF16. */
+int dad_eval_split(const dad_eval_args* args, void* workspace, void* stream);
 
 /* --- the reference's helper types as operators (I/utils.py:317-652) -------------------
  * For trainer code that drives DataAugmentation / DACPManager / ECDALoss itself (the

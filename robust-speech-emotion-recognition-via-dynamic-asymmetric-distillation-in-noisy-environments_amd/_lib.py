@@ -10,7 +10,7 @@ from . import _build
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 
-DAD_ABI_VERSION = 7        # dad.h DAD_ABI_VERSION this binding mirrors
+DAD_ABI_VERSION = 8        # dad.h DAD_ABI_VERSION this binding mirrors
 DAD_NPARAM = 256 * 768 + 256 + 4 * 256 + 4
 DAD_GRAD_EXTRA = 16
 DAD_GRAD_FLOATS = DAD_NPARAM + DAD_GRAD_EXTRA
@@ -31,6 +31,12 @@ RANGE_NONFINITE, RANGE_POOL_TIMEOUT = 1, 2   # bits of the T_RANGE word (dad.h D
 
 def tail_floats(bn):
     return DAD_TAIL_HDR + bn * 7
+
+
+# result block of dad_eval_split (dad.h DAD_EV_*): int64 counts, then float64 moments [4][3]
+EV_CONF_STUDENT, EV_CONF_TEACHER, EV_DISAGREE, EV_N, EV_N_LABELLED, EV_N_SKIPPED, EV_N_NONFINITE = 0, 16, 32, 33, 34, 35, 36
+EV_COUNTS = 40
+EV_MOMENTS, EV_M_COUNT, EV_M_MEAN, EV_M_VAR = 3, 0, 1, 2
 
 
 class DadConfig(ctypes.Structure):
@@ -66,6 +72,14 @@ class DadState(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in
                 ("student", "teacher", "exp_avg", "exp_avg_sq", "grad", "w1bf_student", "w1bf_teacher",
                  "dacp", "tail", "emb", "logits", "losses")]
+
+
+class DadEvalArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_void_p) for n in
+                 ("store", "rows", "lens", "labels", "slab_off", "student", "teacher", "emb", "logits", "probs",
+                  "score", "pred", "t_emb", "t_logits", "t_pred", "counts", "moments")]
+                + [("n", ctypes.c_int64), ("slabs", ctypes.c_int64), ("store_dtype", ctypes.c_int32),
+                   ("use_entropy", ctypes.c_int32), ("precision", ctypes.c_int32), ("reserved", ctypes.c_int32)])
 
 
 # exported symbols (must match include/dad.h); tests check every one is present
@@ -124,6 +138,8 @@ EXPORTS = {
     "dad_predict_head": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p]),
+    "dad_eval_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "dad_eval_split": (ctypes.c_int, [ctypes.POINTER(DadEvalArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "dad_augment": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -9,12 +9,17 @@ Every batch runs the HIP encoder forward (dad_encoder_forward, fp32 as the refer
 dad_predict_head (csrc/eval.hip: classifier, softmax, certainty score, argmax); predictions,
 scores and labels stay on the device until one copy at the end of the loader, where the metrics
 are computed with the same scikit-learn calls the reference makes.
+
+For a split held in a FeatureStore, the whole-split forms do the same in one fused pass
+(dad_eval_split, csrc/eval_split.hip) and report the same values:
+
+  validate_store, calibrate_anchors_store, embed_store, evaluate_store, EvalPlan, metrics_from_confusion
 """
 import numpy as np
 import torch
 
 from . import _lib
-from .data import StoreFeats
+from .data import STORE_DTYPES, StoreFeats
 
 
 def _feats_mask(batch, device):
@@ -108,3 +113,232 @@ def calibrate_anchors(model, clean_loader, noisy_loader, num_classes=4, anchor_s
     base = torch.clamp(mu_c - anchor_std_k * sd_c, min=0)
     model.train()
     return base * shift
+
+
+# ------------------------------------------------------------------ whole-split, store-fed
+# The functions above take any loader and work batch by batch (a padded batch, four output
+# tensors and three launches per batch, a second sweep for the teacher, scikit-learn on
+# per-utterance arrays).  Those below take a FeatureStore split: dad_eval_split
+# (csrc/eval_split.hip) reads every utterance's rows in place, runs student and teacher on one
+# read, and builds the confusion matrices, the disagreement count and the per-class score
+# moments on the device; one copy of 52 words returns them.
+
+_PRECISIONS = {"fp32": _lib.PREC_FP32, "fp16": _lib.PREC_FP16, "bf16": _lib.PREC_BF16}
+_OUTPUTS = {"emb": ((256,), torch.float32), "logits": ((4,), torch.float32), "probs": ((4,), torch.float32),
+            "score": ((), torch.float32), "pred": ((), torch.int64), "t_emb": ((256,), torch.float32),
+            "t_logits": ((4,), torch.float32), "t_pred": ((), torch.int64)}
+_RESULT_WORDS = _lib.EV_COUNTS + 4 * _lib.EV_MOMENTS
+
+
+def plan_host(sizes, offsets):
+    """The host side of an EvalPlan, a pure function of a store's per-sample sizes / offsets:
+    (rows int64 [n], lens int32 [n], slab_off int32 [n + 1]).  Utterance i is store rows
+    [rows[i], rows[i] + lens[i]) (row 0 for an empty one: nothing of it is read) and owns the
+    32-frame slab jobs [slab_off[i], slab_off[i + 1]), ceil(lens[i] / 32) of them."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    if sizes.shape != offsets.shape:
+        raise ValueError("sizes and offsets differ in length")
+    if len(sizes) and (sizes.min() < 0 or sizes.max() >= 2 ** 31):
+        raise ValueError("sample sizes must be in [0, 2^31)")
+    nslab = (sizes + 31) // 32
+    slab_off = np.concatenate([[0], np.cumsum(nslab)])
+    if slab_off[-1] >= 2 ** 31:
+        raise ValueError("the split holds %d slabs; the evaluator indexes them with 32 bits" % slab_off[-1])
+    rows = np.where(sizes > 0, offsets, 0).astype(np.int64)
+    return rows, sizes.astype(np.int32), slab_off.astype(np.int32)
+
+
+def slab_jobs(slab_off):
+    """(utterance, slab within it) of every job of a plan_host prefix, by the kernel's rule: job j
+    belongs to the largest i < n with slab_off[i] <= j."""
+    slab_off = np.asarray(slab_off, dtype=np.int64)
+    jobs = np.arange(slab_off[-1], dtype=np.int64)
+    utt = np.searchsorted(slab_off[:-1], jobs, side="right") - 1
+    return utt, jobs - slab_off[utt]
+
+
+class EvalPlan:
+    """Everything dad_eval_split needs about one split that does not change between epochs: the
+    per-utterance rows / lengths / slab prefix on the device (built once with NumPy from the
+    store's host sizes / offsets), the labels, and the reusable workspace and result buffers.
+    Accepts a FeatureStore or a DeviceLoader over one (its .store; sample order is the store's
+    and is irrelevant to every split-wide output).  EvalPlan.of caches the plan on the store."""
+
+    def __init__(self, store_or_loader):
+        store = getattr(store_or_loader, "store", store_or_loader)
+        if not hasattr(store, "feats") or not hasattr(store, "offsets"):
+            raise TypeError("EvalPlan needs a FeatureStore or a DeviceLoader over one, got %s"
+                            % type(store_or_loader).__name__)
+        rows, lens, slab_off = plan_host(store.sizes, store.offsets)
+        if len(lens) == 0:
+            raise ValueError("the split is empty")
+        self.store = store
+        self.n = len(lens)
+        self.slabs = int(slab_off[-1])
+        self.frames = int(lens.astype(np.int64).sum())
+        dev = torch.device(store.device)
+        self.device = dev
+        self.rows_d = torch.from_numpy(rows).to(dev)
+        self.lens_d = torch.from_numpy(lens).to(dev)
+        self.slab_off_d = torch.from_numpy(slab_off).to(dev)
+        self.labels_d = store.labels_d
+        self.result_d = torch.zeros(_RESULT_WORDS, dtype=torch.int64, device=dev)
+        self.result_h = torch.zeros(_RESULT_WORDS, dtype=torch.int64).pin_memory()
+        self._ws = None
+
+    @classmethod
+    def of(cls, x):
+        if isinstance(x, cls):
+            return x
+        store = getattr(x, "store", x)
+        plan = getattr(store, "_eval_plan", None)
+        if plan is None:
+            plan = cls(store)
+            store._eval_plan = plan
+        return plan
+
+    def workspace(self, precision, with_teacher):
+        need = int(_lib.lib().dad_eval_workspace_bytes(self.n, self.slabs, precision, int(with_teacher)))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+
+def enqueue_eval_split(model, plan, use_teacher=False, use_entropy=True, precision="fp32", outputs=()):
+    """dad_eval_split on the current stream, enqueue only (no copy, no synchronisation): the result
+    block lands in plan.result_d.  Returns the {name: device tensor} of the requested outputs."""
+    prec = _PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    dev = plan.device
+    if model.student_flat.device != dev:
+        raise RuntimeError("model on %s, store on %s" % (model.student_flat.device, dev))
+    out = {}
+    for name in outputs:
+        if name not in _OUTPUTS:
+            raise ValueError("unknown output %r (one of %s)" % (name, ", ".join(_OUTPUTS)))
+        if name.startswith("t_") and not use_teacher:
+            raise ValueError("output %r needs use_teacher=True" % name)
+        shape, dt = _OUTPUTS[name]
+        out[name] = torch.empty((plan.n,) + shape, dtype=dt, device=dev)
+    store = plan.store
+    a = _lib.DadEvalArgs()
+    a.store = store.feats.data_ptr()
+    a.rows, a.lens, a.slab_off = plan.rows_d.data_ptr(), plan.lens_d.data_ptr(), plan.slab_off_d.data_ptr()
+    a.labels = None if plan.labels_d is None else plan.labels_d.data_ptr()
+    a.student = model.student_flat.data_ptr()
+    a.teacher = model.teacher_flat.data_ptr() if use_teacher else None
+    for name, t in out.items():
+        setattr(a, name, t.data_ptr())
+    a.counts = plan.result_d.data_ptr()
+    a.moments = plan.result_d.data_ptr() + 8 * _lib.EV_COUNTS
+    a.n, a.slabs = plan.n, plan.slabs
+    a.store_dtype = STORE_DTYPES[store.feats.dtype]
+    a.use_entropy = int(bool(use_entropy))
+    a.precision = prec
+    ws = plan.workspace(prec, use_teacher)
+    stream = torch.cuda.current_stream(dev)
+    _lib.check(_lib.lib().dad_eval_split(a, _lib.ptr(ws), stream.cuda_stream), "dad_eval_split")
+    return out
+
+
+def evaluate_store(model, plan_or_store, use_teacher=False, use_entropy=True, precision="fp32", outputs=()):
+    """One dad_eval_split over the whole split and one device-to-host copy of its result block.
+    Returns {'confusion_student' [4,4], 'confusion_teacher' [4,4], 'disagree', 'n', 'n_labelled',
+    'n_skipped', 'n_nonfinite', 'moments' [4,3] (count, mean, population variance of the student's
+    certainty score per true class)} as NumPy values, plus a device tensor per name in `outputs`
+    ('emb', 'logits', 'probs', 'score', 'pred', 't_emb', 't_logits', 't_pred'; store sample order).
+    precision 'fp32' (the reference's eval arithmetic) or 'fp16'.  Raises DadError when any
+    utterance has a non-finite logit."""
+    plan = EvalPlan.of(plan_or_store)
+    out = enqueue_eval_split(model, plan, use_teacher, use_entropy, precision, outputs)
+    stream = torch.cuda.current_stream(plan.device)
+    plan.result_h.copy_(plan.result_d, non_blocking=True)
+    stream.synchronize()
+    host = plan.result_h.numpy().copy()
+    counts = host[:_lib.EV_COUNTS]
+    res = {
+        "confusion_student": counts[_lib.EV_CONF_STUDENT:_lib.EV_CONF_STUDENT + 16].reshape(4, 4).copy(),
+        "confusion_teacher": counts[_lib.EV_CONF_TEACHER:_lib.EV_CONF_TEACHER + 16].reshape(4, 4).copy(),
+        "disagree": int(counts[_lib.EV_DISAGREE]), "n": int(counts[_lib.EV_N]),
+        "n_labelled": int(counts[_lib.EV_N_LABELLED]), "n_skipped": int(counts[_lib.EV_N_SKIPPED]),
+        "n_nonfinite": int(counts[_lib.EV_N_NONFINITE]),
+        "moments": host[_lib.EV_COUNTS:].view(np.float64).reshape(4, _lib.EV_MOMENTS).copy(),
+        "block": host,
+    }
+    if res["n_nonfinite"] > 0:
+        raise _lib.DadError("dad_eval_split: %d of %d utterance(s) have a non-finite logit (fp16: an operand beyond "
+                            "+-65504; any precision: non-finite features)" % (res["n_nonfinite"], res["n"]))
+    res.update(out)
+    return res
+
+
+def metrics_from_confusion(cm):
+    """Every key validate() returns (but 'disagreement_rate'), from the confusion matrix alone
+    (row = label, column = prediction), with scikit-learn's conventions: zero_division = 0;
+    balanced accuracy averages recall over the classes present in y_true; the macro / weighted F1
+    (no labels= argument) average over the classes present in y_true or y_pred; the *_per_class
+    arrays cover range(num_classes)."""
+    cm = np.asarray(cm)
+    if cm.ndim != 2 or cm.shape[0] != cm.shape[1]:
+        raise ValueError("confusion matrix must be square")
+    cm = cm.astype(np.int64)
+    total = int(cm.sum())
+    if total == 0:
+        raise ValueError("no labelled utterances")
+    tp = np.diag(cm).astype(np.float64)
+    sup = cm.sum(1)
+    npred = cm.sum(0)
+    div = lambda a, b: np.divide(a, b, out=np.zeros(len(a), np.float64), where=b > 0)
+    prec = div(tp, npred.astype(np.float64))
+    rec = div(tp, sup.astype(np.float64))
+    f1 = div(2.0 * tp, (sup + npred).astype(np.float64))      # 2tp / (2tp + fp + fn)
+    present = (sup > 0) | (npred > 0)
+    return {
+        "accuracy": float(tp.sum() / total) * 100,
+        "weighted_accuracy": float(np.mean(rec[sup > 0])) * 100,
+        "f1_weighted": float(np.sum(f1[present] * sup[present]) / sup[present].sum()) * 100,
+        "f1_macro": float(np.mean(f1[present])) * 100,
+        "precision_per_class": prec.tolist(), "recall_per_class": rec.tolist(),
+        "f1_per_class": f1.tolist(), "support_per_class": sup.tolist(), "confusion_matrix": cm,
+    }
+
+
+def validate_store(model, store_or_loader, domain_name="unknown", num_classes=4, teacher_disagreement=False,
+                   precision="fp32"):
+    """validate() over a FeatureStore split in one fused pass: the same dict, 'disagreement_rate'
+    from the same pass (the teacher runs on the student's row reads)."""
+    if num_classes != 4:
+        raise ValueError("the MI355X kernels are built for 4 classes")
+    model.eval()
+    r = evaluate_store(model, store_or_loader, use_teacher=teacher_disagreement, precision=precision)
+    res = {}
+    if teacher_disagreement:
+        res["disagreement_rate"] = r["disagree"] / r["n"]
+    res.update(metrics_from_confusion(r["confusion_student"]))
+    return res
+
+
+def calibrate_anchors_store(model, clean, noisy, num_classes=4, anchor_std_k=1.5, use_entropy=True):
+    """calibrate_anchors() over two FeatureStore splits, from the moments block of one
+    dad_eval_split each (float64 mean / population std of the float32 scores, as np.mean / np.std)."""
+    if num_classes != 4:
+        raise ValueError("the MI355X kernels are built for 4 classes")
+    model.eval()
+    dev = model.student_flat.device
+    mom = {name: evaluate_store(model, s, use_entropy=use_entropy)["moments"]
+           for name, s in (("clean", clean), ("noisy", noisy))}
+    mu_c = torch.tensor(mom["clean"][:, _lib.EV_M_MEAN].tolist(), device=dev)
+    mu_n = torch.tensor(mom["noisy"][:, _lib.EV_M_MEAN].tolist(), device=dev)
+    sd_c = torch.tensor(np.sqrt(mom["clean"][:, _lib.EV_M_VAR]).tolist(), device=dev)
+    shift = mu_n / (mu_c + 1e-8)
+    base = torch.clamp(mu_c - anchor_std_k * sd_c, min=0)
+    model.train()
+    return base * shift
+
+
+def embed_store(model, store_or_loader, use_teacher=False):
+    """Eval-mode embeddings [n, 256] of every utterance of the split, in the store's sample order
+    (the split-wide use of SSRLModel.get_embeddings, I/model.py:247-265), on the device."""
+    model.eval()
+    name = "t_emb" if use_teacher else "emb"
+    return evaluate_store(model, store_or_loader, use_teacher=use_teacher, outputs=(name,))[name]
