@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DAD_ABI_VERSION 8
+#define DAD_ABI_VERSION 9
 
 /* error codes (besides hipError_t values) */
 #define DAD_OK 0
@@ -172,7 +172,7 @@ typedef struct dad_state {
 } dad_state;
 
 /* --- sizing ------------------------------------------------------------------------ */
-/* DAD_ABI_VERSION the library was built with (ABI 8; 7 lacked dad_eval_split, 6 dad_timing_reset): a binding compares it with the header's
+/* DAD_ABI_VERSION the library was built with (ABI 9; 8 lacked dad_step_plan, 7 dad_eval_split, 6 dad_timing_reset): a binding compares it with the header's
  * value when it loads the library, so a stale build fails at load instead of at a call. */
 int dad_abi_version(void);
 size_t dad_param_count(void);
@@ -237,6 +237,34 @@ int dad_step_backward_ahead_split(const dad_config* cfg, const dad_batch* batch,
  * DAD_PREP_NOISY) into the workspace's prepared set of cfg->counter's parity -- the set the step with this
  * cfg reads (dad_prep; the draws of cfg's counter).  DAD_E_UNSUPPORTED in FP32. */
 int dad_step_prepare_rows(const dad_config* cfg, const dad_batch* batch, void* workspace, void* stream, int parts);
+/* Host-only (ABI 9): the launches the step with cfg makes on a device of `cus` compute units -- the plan
+ * the step itself enqueues from -- when its backward is dad_step_backward_ahead_split(.., next_cfg,
+ * next_batch, defer, ..) (next_cfg = next_batch = NULL, defer = 0: dad_step_backward).  No device call;
+ * the batch pointers are only tested for NULL, never followed.  A grid of 0 = that launch is not made;
+ * kernel names are static strings.  Returns cfg's validation code, or DAD_E_ARG for cus < 2, out = NULL
+ * or defer bits outside DAD_PREP_*; a next step that does not qualify for preparation ahead is no
+ * error (prepped = 0).  Diagnostics and tests. */
+typedef struct dad_step_plan_info {
+  int32_t splits, max_splits;   /* weight-gradient split-K factor of this step; the one the workspace is sized for */
+  int32_t prep_grid;            /* standalone dad_prep of this step's rows before the encoder (cfg->prepped = 0) */
+  int32_t encode_grid;
+  int32_t ws_nt, ws_ns;         /* 16-bit encoder: teacher / student workgroups (dad_encoder_ws_plan) */
+  int32_t pool_grid;            /* separate dad_pool; 0: the tail launch pools */
+  int32_t tail_grid;
+  int32_t tail_prep;            /* DAD_PREP_* parts of the next batch's rows the tail launch prepares */
+  int32_t tail_prep_clean_only; /* that set holds clean rows only */
+  int32_t wgrad_grid;
+  int32_t wgrad_clean;          /* the weight gradient converts the next batch's clean rows */
+  int32_t wgrad_store;          /* ... gathered through that batch's rowc / lenc table */
+  int32_t reduce_grid;
+  int32_t prepped, pending;     /* as dad_step_backward_ahead_split reports them */
+  const char* encode;           /* dad_encode_wp_f16 / dad_encode_wp / dad_encode_f32 */
+  const char* tail;             /* dad_tail_ecda_w / dad_tail_ecda / dad_tail */
+  const char* wgrad;            /* dad_wgrad_direct[_f16][_cp|_cps] / dad_wgrad_f32 */
+  const char* reduce;           /* dad_reduce_w / dad_reduce */
+} dad_step_plan_info;
+int dad_step_plan(const dad_config* cfg, const dad_config* next_cfg, const dad_batch* next_batch, int defer,
+                  int cus, dad_step_plan_info* out);
 int dad_step_apply(const dad_config* cfg, const dad_state* st, void* workspace, void* stream);
 int dad_step(const dad_config* cfg, const dad_batch* batch, const dad_state* st,
              void* workspace, void* stream);
@@ -451,7 +479,7 @@ int dad_rng_draws(const dad_config* cfg, int which, uint64_t first, size_t n, fl
  * session is active: stop the first before starting another. */
 #define DAD_TK_ENCODE 0       /* dad_encode_ws[_f16] / dad_encode_f32 */
 #define DAD_TK_POOL 1         /* dad_pool */
-#define DAD_TK_TAIL 2         /* dad_tail_ecda_w / dad_tail_ecda (or dad_tail + dad_ecda) */
+#define DAD_TK_TAIL 2         /* dad_tail_ecda_w / dad_tail_ecda (warm-up: dad_tail) */
 #define DAD_TK_WGRAD 3        /* dad_wgrad_direct (FP16/BF16) / dad_wgrad_f32 (FP32) */
 #define DAD_TK_REDUCE 4       /* dad_reduce_w (FP16/BF16) / dad_reduce (FP32) */
 #define DAD_TK_OPTIM 5        /* dad_optim */

@@ -10,7 +10,7 @@ from . import _build
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 
-DAD_ABI_VERSION = 8        # dad.h DAD_ABI_VERSION this binding mirrors
+DAD_ABI_VERSION = 9        # dad.h DAD_ABI_VERSION this binding mirrors
 DAD_NPARAM = 256 * 768 + 256 + 4 * 256 + 4
 DAD_GRAD_EXTRA = 16
 DAD_GRAD_FLOATS = DAD_NPARAM + DAD_GRAD_EXTRA
@@ -74,6 +74,14 @@ class DadState(ctypes.Structure):
                  "dacp", "tail", "emb", "logits", "losses")]
 
 
+class DadStepPlanInfo(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in
+                 ("splits", "max_splits", "prep_grid", "encode_grid", "ws_nt", "ws_ns", "pool_grid", "tail_grid",
+                  "tail_prep", "tail_prep_clean_only", "wgrad_grid", "wgrad_clean", "wgrad_store", "reduce_grid",
+                  "prepped", "pending")]
+                + [(n, ctypes.c_char_p) for n in ("encode", "tail", "wgrad", "reduce")])
+
+
 class DadEvalArgs(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_void_p) for n in
                  ("store", "rows", "lens", "labels", "slab_off", "student", "teacher", "emb", "logits", "probs",
@@ -108,6 +116,8 @@ EXPORTS = {
                                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "dad_step_prepare_rows": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.POINTER(DadBatch), ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_int]),
+    "dad_step_plan": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.POINTER(DadConfig), ctypes.POINTER(DadBatch),
+                                     ctypes.c_int, ctypes.c_int, ctypes.POINTER(DadStepPlanInfo)]),
     "dad_step_apply": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.POINTER(DadState),
                                       ctypes.c_void_p, ctypes.c_void_p]),
     "dad_step": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.POINTER(DadBatch), ctypes.POINTER(DadState),

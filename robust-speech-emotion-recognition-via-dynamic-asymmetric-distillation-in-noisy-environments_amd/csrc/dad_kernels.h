@@ -10,12 +10,10 @@
 #define DAD_POOL_THREADS 64
 #define DAD_TAIL_THREADS 512
 #define DAD_ECDA_THREADS 512
-// 1: the tail and ECDA run as one launch (dad_tail_ecda): block 0 is the tail, blocks 1..C
-// re-derive the DACP mask themselves and go straight on to ECDA (no kernel boundary and no
-// round trip of the mask through HBM).  0: dad_tail then dad_ecda (A/B builds).
-#ifndef DAD_FUSED_TAIL
-#define DAD_FUSED_TAIL 1
-#endif
+// The tail and ECDA run as one launch (dad_tail_ecda / dad_tail_ecda_w): block 0 is the tail,
+// blocks 1..C re-derive the DACP mask themselves and go straight on to ECDA (no kernel boundary
+// and no round trip of the mask through HBM).  dad_tail alone: warm-up steps; dad_ecda alone: the
+// modular dad_ecda_loss.
 #define DAD_WGRAD_THREADS 256
 // dad_wgrad_direct (FP16/BF16): 64-column blocks, slab-range splits of at most WGD_MAXU slabs,
 // WGD_DEPTH slabs in flight per group, x tile row pitch WGD_XP halves (192 B)

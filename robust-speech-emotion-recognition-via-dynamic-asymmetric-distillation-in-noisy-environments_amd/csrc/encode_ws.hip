@@ -30,7 +30,7 @@
 //
 // Roles are per workgroup: TEACHER workgroups (teacher W1) run the weak slabs, STUDENT workgroups
 // (student W1) the clean slabs and then the strong slabs, contiguous ranges balanced by live
-// sub-slabs (dad_wp_job_range; host: wp_split in dad_abi.hip); a job whose second 16 rows hold no
+// sub-slabs (dad_wp_job_range; host: wp_split in step_plan.h); a job whose second 16 rows hold no
 // frame multiplies only the first.
 #include <type_traits>
 

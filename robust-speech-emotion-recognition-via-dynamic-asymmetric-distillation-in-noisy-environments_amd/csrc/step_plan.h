@@ -1,0 +1,215 @@
+// The host plan of one DAD step: which kernels its launches are and how large their grids, decided
+// in one place (plan_step) from the configs and the presence of batch pointers.  Host code only:
+// no HIP call, no allocation, nothing read through a batch pointer.  The step's enqueue code
+// (dad_abi.hip) launches what the plan says; dad_step_plan (dad.h) shows the same plan to tests.
+#pragma once
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "dad_kernels.h"
+
+inline int check_cfg(const dad_config* c) {
+  if (!c) return DAD_E_ARG;
+  if (c->B < 1 || c->B > DAD_MAX_BATCH || c->T < 1) return DAD_E_SHAPE;
+  if (c->Bn < 0 || c->Bn > DAD_MAX_BATCH || c->Tn < 0) return DAD_E_SHAPE;
+  if (!c->warmup && (c->Bn < 1 || c->Tn < 1)) return DAD_E_SHAPE;
+  if (c->precision != DAD_PREC_FP32 && !dad_prec16(c->precision)) return DAD_E_ARG;
+  if (c->rng_mode != DAD_RNG_EXPLICIT && c->rng_mode != DAD_RNG_COUNTER) return DAD_E_ARG;
+  if (c->dp_world < 1) return DAD_E_ARG;
+  return DAD_OK;
+}
+
+inline DadGeom geom_of(const dad_config* c) { return dad_geom(c->B, c->T, c->Bn, c->Tn); }
+
+// Batch-pointer checks shared by the step, can_prepare_ahead and dad_step_prepare_rows.
+// Store mode, per batch (clean and noisy independently): rows and lengths come together.
+inline bool rows_paired(const dad_batch* b) {
+  return (b->rowc == nullptr) == (b->lenc == nullptr) && (b->rown == nullptr) == (b->lenn == nullptr);
+}
+// DAD_RNG_EXPLICIT: the augmentation's four draws of a noisy batch
+inline bool has_explicit_draws(const dad_batch* b) { return b->nw && b->ns && b->u && b->start; }
+
+inline int splits_of(const dad_config* c) {
+  const DadGeom g = geom_of(c);
+  if (c->splits <= 0) return dad_auto_splits(g, c->precision, c->warmup);
+  if (!dad_prec16(c->precision)) return c->splits;
+  // dad_wgrad_direct holds at most WGD_MAXU slabs' utterances per split
+  const int total = g.Bc * g.ncc + (c->warmup ? 0 : g.Bn * g.ncn);
+  return std::max(c->splits, dad_wgd_min_splits(total));
+}
+
+inline int max_splits_of(const dad_config* c) {
+  // the workspace is sized for the largest split count any step with this geometry may use
+  const int s = splits_of(c);
+  if (!c->warmup) return s;
+  dad_config post = *c;
+  post.warmup = 0;
+  return std::max(s, splits_of(&post));
+}
+
+// DAD_TAIL_W=0 selects the general tail + ECDA launch for every batch (A/B runs; read once)
+inline bool tail_w_on() {
+  static const bool on = [] { const char* e = getenv("DAD_TAIL_W"); return !(e && strcmp(e, "0") == 0); }();
+  return on;
+}
+
+// Roles of the prepared-row encoder (dad_encode_wp, dad_wp_job_range): nt teacher and ns student
+// workgroups, one per CU, in proportion to their live 16-row sub-slabs (every prepared sub-slab
+// costs the same); more workgroups than CUs only when a range would exceed the kernel's
+// DAD_ENC_WS_MAXJ-job table.
+inline int wp_max_range(const DadGeom& G, int Bn, int nt, int ns) {
+  int worst = 0;
+  for (int wg = 0; wg < nt + ns; ++wg) {
+    bool t = false;
+    int j0 = 0, j1 = 0;
+    dad_wp_job_range(wg, nt, ns, G.Bc, G.Tc, G.ncc, Bn, G.Tn, G.ncn, Bn * G.ncn, t, j0, j1);
+    worst = std::max(worst, j1 - j0);
+  }
+  return worst;
+}
+inline int wp_split(const DadGeom& G, int Bn, int cus, int& nt, int& ns) {
+  struct Entry { int Bc, Tc, Bn, Tn, cus, rc, nt, ns; };
+  static thread_local Entry last{-1, -1, -1, -1, -1, 0, 0, 0};
+  if (!(last.Bc == G.Bc && last.Tc == G.Tc && last.Bn == Bn && last.Tn == G.Tn && last.cus == cus)) {
+    Entry e{G.Bc, G.Tc, Bn, G.Tn, cus, 0, 0, 0};
+    const int Js = Bn * G.ncn, Jc = G.Bc * G.ncc;
+    const double ln = (double)Bn * ((G.Tn + 15) / 16), lc = (double)G.Bc * ((G.Tc + 15) / 16);
+    if (Js == 0) {
+      e.ns = std::min(cus, Jc);
+    } else {
+      e.nt = std::max(1, std::min(std::min(Js, cus - 1), (int)(cus * ln / (2.0 * ln + lc) + 0.5)));
+      e.ns = std::min(cus - e.nt, Jc + Js);
+    }
+    while (e.rc == DAD_OK && wp_max_range(G, Bn, e.nt, e.ns) > DAD_ENC_WS_MAXJ) {
+      if (e.nt > 0 && e.nt < Js) ++e.nt;
+      if (e.ns < Jc + Js) ++e.ns;
+      if (e.nt + e.ns > Js + Jc + 2) e.rc = DAD_E_SHAPE;
+    }
+    last = e;
+  }
+  nt = last.nt;
+  ns = last.ns;
+  return last.rc;
+}
+
+// standalone dad_prep: ~4 workgroups of 4 waves per CU, two rows in flight per wave
+inline int prep_grid_of(int cus) { return 4 * cus; }
+
+// The kernels a step launches;kStepKernelName spells them as the profile tools do.
+enum StepKernel {
+  K_ENCODE_F32, K_ENCODE_WP, K_ENCODE_WP_F16,
+  K_TAIL, K_TAIL_ECDA, K_TAIL_ECDA_W,
+  K_WGRAD_F32, K_WGRAD_DIRECT, K_WGRAD_DIRECT_CP, K_WGRAD_DIRECT_CPS,
+  K_WGRAD_DIRECT_F16, K_WGRAD_DIRECT_F16_CP, K_WGRAD_DIRECT_F16_CPS,
+  K_REDUCE, K_REDUCE_W, K_COUNT
+};
+constexpr const char* kStepKernelName[K_COUNT] = {
+    "dad_encode_f32", "dad_encode_wp", "dad_encode_wp_f16",
+    "dad_tail", "dad_tail_ecda", "dad_tail_ecda_w",
+    "dad_wgrad_f32", "dad_wgrad_direct", "dad_wgrad_direct_cp", "dad_wgrad_direct_cps",
+    "dad_wgrad_direct_f16", "dad_wgrad_direct_f16_cp", "dad_wgrad_direct_f16_cps",
+    "dad_reduce", "dad_reduce_w"};
+// the 16-bit weight gradient by [fp16][takes the next batch's clean rows][through its store table]
+constexpr StepKernel kWgradDirect[2][2][2] = {
+    {{K_WGRAD_DIRECT, K_WGRAD_DIRECT}, {K_WGRAD_DIRECT_CP, K_WGRAD_DIRECT_CPS}},
+    {{K_WGRAD_DIRECT_F16, K_WGRAD_DIRECT_F16}, {K_WGRAD_DIRECT_F16_CP, K_WGRAD_DIRECT_F16_CPS}}};
+
+struct StepPlan {
+  int splits, max_splits;       // this step's split-K factor; the one its workspace is laid out for
+  int prep_grid;                // standalone dad_prep of this step's rows before the encoder (all parts); 0: none
+  StepKernel encode;
+  int encode_grid, ws_nt, ws_ns;   // (ws_nt / ws_ns: dad_encode_wp's roles; encode_rc: wp_split's code)
+  int encode_rc;
+  int pool_grid;                // the separate dad_pool; 0: the tail launch pools
+  StepKernel tail;
+  int tail_grid;
+  int tail_prep;                // DAD_PREP_* parts of the NEXT batch the tail launch prepares
+  StepKernel wgrad;
+  int wgrad_grid, wgrad_tiles;
+  int wgrad_clean, wgrad_store;    // it converts the next batch's clean rows; through that batch's store table
+  StepKernel reduce;
+  int reduce_grid;
+  int prepped, pending;         // as dad_step_backward_ahead_split reports them
+};
+
+// The next step's batch may be prepared in this step's launches when the tail runs as
+// dad_tail_ecda_w and the next step has this step's workspace layout (so its prepared set sits
+// where the next step will look) and the other set parity.
+inline bool can_prepare_ahead(const dad_config* cfg, int max_splits, const dad_config* ncfg, const dad_batch* nbt) {
+  if (!ncfg || !nbt || check_cfg(ncfg) != DAD_OK) return false;
+  if (!dad_prec16(cfg->precision) || ncfg->precision != cfg->precision) return false;
+  if (ncfg->B != cfg->B || ncfg->T != cfg->T || ncfg->Bn != cfg->Bn || ncfg->Tn != cfg->Tn) return false;
+  if (((ncfg->counter ^ cfg->counter) & 1u) == 0) return false;
+  if (max_splits_of(ncfg) != max_splits) return false;
+  if (!nbt->xc || !nbt->mc) return false;
+  if (!ncfg->warmup && (!nbt->xn || !nbt->mn)) return false;
+  if (ncfg->rng_mode == DAD_RNG_EXPLICIT && !ncfg->warmup && !has_explicit_draws(nbt)) return false;
+  return rows_paired(nbt);
+}
+
+// cfg: a config check_cfg accepts.  (next_cfg, next_batch): the step after it, or NULL; one that does
+// not qualify (can_prepare_ahead) is prepared by its own step.  defer: the DAD_PREP_* parts of the
+// next batch's rows this step's launches leave to the caller (dad_step_prepare_rows).  cus: the
+// device's compute units.
+inline StepPlan plan_step(const dad_config* cfg, const dad_config* next_cfg, const dad_batch* next_batch, int defer,
+                          int cus) {
+  StepPlan p = {};
+  const DadGeom G = geom_of(cfg);
+  const int Bn = cfg->warmup ? 0 : G.Bn;
+  const bool h16 = dad_prec16(cfg->precision), f16 = cfg->precision == DAD_PREC_FP16;
+  p.splits = splits_of(cfg);
+  p.max_splits = max_splits_of(cfg);
+
+  // encoder.  16-bit: augmentation + conversion (unless the previous step prepared this batch),
+  // then the W-stationary GEMM on the prepared set.  FP32: one wave per 32-row slab, four per
+  // workgroup.
+  if (h16) {
+    if (!cfg->prepped) p.prep_grid = prep_grid_of(cus);
+    p.encode_rc = wp_split(G, Bn, cus, p.ws_nt, p.ws_ns);
+    p.encode = f16 ? K_ENCODE_WP_F16 : K_ENCODE_WP;
+    p.encode_grid = p.ws_nt + p.ws_ns;
+  } else {
+    p.encode = K_ENCODE_F32;
+    p.encode_grid = (G.Bc * G.ncc + Bn * G.ncn + 3) / 4;
+  }
+
+  // pooling and tail.  Batches of at most 64 utterances per side with class-aware MMD, after the
+  // warm-up: the wave-centric launch, whose spare blocks pool the embeddings (one item per wave,
+  // Bc + 2 Bn items) instead of a separate dad_pool launch.  Warm-up: no ECDA.  Otherwise block 0 is
+  // the tail and blocks 1..C the classes.
+  const bool tail_w = !cfg->warmup && G.Bc <= 64 && Bn <= 64 && cfg->class_aware && tail_w_on();
+  const int items = G.Bc + 2 * Bn, waves = DAD_TAIL_THREADS / 64;
+  if (!tail_w) p.pool_grid = items;
+  p.tail = cfg->warmup ? K_TAIL : tail_w ? K_TAIL_ECDA_W : K_TAIL_ECDA;
+  p.tail_grid = cfg->warmup ? 1 : 1 + DAD_C + (tail_w ? (items + waves - 1) / waves : 0);
+
+  // preparation ahead: the next batch's clean rows in the weight-gradient launch (interleaved with
+  // the GEMM), its noisy rows on the CUs the tail and class blocks leave idle
+  if (tail_w && can_prepare_ahead(cfg, p.max_splits, next_cfg, next_batch)) {
+    p.prepped = 1;
+    p.pending = defer & (DAD_PREP_CLEAN | DAD_PREP_NOISY);
+    p.wgrad_clean = !(defer & DAD_PREP_CLEAN);
+    p.wgrad_store = p.wgrad_clean && next_batch->rowc != nullptr;
+    p.tail_prep = (defer & DAD_PREP_NOISY) ? 0 : DAD_PREP_NOISY;
+    if (p.tail_prep) p.tail_grid = std::max(p.tail_grid, std::max(cus, 2 * (1 + DAD_C)));
+  }
+
+  // weight gradient and the split sums.  16-bit: WGD_NDB column blocks per split, the grid a
+  // multiple of 8 (XCD-aware tile order) with WGD_XWG spare workgroups for the reduce's extra blocks.
+  // FP32: one tile = (split, 128 columns); then every reduce block.
+  if (h16) {
+    p.wgrad = kWgradDirect[f16][p.wgrad_clean][p.wgrad_store];
+    p.wgrad_tiles = WGD_NDB * p.splits;
+    p.wgrad_grid = (p.wgrad_tiles + WGD_XWG + 7) / 8 * 8;
+    p.reduce = K_REDUCE_W;
+    p.reduce_grid = DAD_REDUCE_BLOCKS - DAD_REDUCE_XBLK;
+  } else {
+    p.wgrad = K_WGRAD_F32;
+    p.wgrad_tiles = p.wgrad_grid = 6 * p.splits;
+    p.reduce = K_REDUCE;
+    p.reduce_grid = DAD_REDUCE_BLOCKS;
+  }
+  return p;
+}

@@ -113,7 +113,8 @@ def test_encoder_job_assignment_covers_every_slab_once(Bc, Tc, Bn, Tn, cus):
 def test_ctypes_structs_match_c_layout(tmp_path):
     """Compile a C probe against include/dad.h and compare sizeof/offsetof with ctypes."""
     p = dadpkg.pkg()
-    fields = {"dad_config": p._lib.DadConfig, "dad_batch": p._lib.DadBatch, "dad_state": p._lib.DadState}
+    fields = {"dad_config": p._lib.DadConfig, "dad_batch": p._lib.DadBatch, "dad_state": p._lib.DadState,
+              "dad_step_plan_info": p._lib.DadStepPlanInfo}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "dad.h"', "int main(void){"]
     for cname, cls in fields.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))

@@ -169,6 +169,45 @@ def test_prepare_rows_matches_step_preparation():
     assert L.dad_step_prepare_rows(dcfg, bt, PKG._lib.ptr(ws), step._stream(), 3) == 1004
 
 
+def test_step_plan_query_reports_what_the_step_does(monkeypatch):
+    """dad_step_plan (ABI 9) is a view of the plan the step enqueues from: for every `defer`, called with
+    the device's CU count and the very structs DADStep.step hands to dad_step_backward_ahead[_split],
+    it reports the prepped / pending that call then returns."""
+    import ctypes
+    import dadpkg
+    lib = dadpkg.pkg()._lib
+    L = lib.lib()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    seen = []
+
+    def spy(name, split):
+        real = getattr(L, name)
+
+        def call(cfg, bt, st, ws, stream, ncfg, nbt, *rest):     # rest: ([defer,] &prepped[, &pending])
+            defer = rest[0] if split else 0
+            info = lib.DadStepPlanInfo()
+            assert L.dad_step_plan(cfg, ncfg, nbt, defer, cus, ctypes.byref(info)) == 0
+            rc = real(cfg, bt, st, ws, stream, ncfg, nbt, *rest)
+            got = (rest[1]._obj.value, rest[2]._obj.value) if split else (rest[0]._obj.value, 0)
+            seen.append((defer, (info.prepped, info.pending), got))
+            return rc
+        monkeypatch.setattr(L, name, call)
+
+    spy("dad_step_backward_ahead", False)
+    spy("dad_step_backward_ahead_split", True)
+    cfg = dad_oracle.make_cfg("iemocap")
+    batches = [_device_batches(_problem(B=16, T=40, seed=81 + i, Bn=12, Tn=50))[:2] for i in range(2)]
+    step = gh.make_step(cfg, precision="fp16", rng="counter", seed=5)
+    gh.load_state(step, synth.make_state(81, 1))
+    for defer in range(4):
+        step.prep_under_exchange = defer
+        step.step(*batches[defer % 2], 60, next_batch=batches[(defer + 1) % 2])
+    torch.cuda.synchronize()
+    assert [s[0] for s in seen] == [0, 1, 2, 3]
+    for defer, planned, got in seen:
+        assert planned == got == (1, defer), (defer, planned, got)
+
+
 def test_timing_reset_counts_only_later_steps():
     """dad_timing_reset (ABI 7, bench.py's warm-up): the steps before the reset are not counted and
     the session's events stay usable: every step timed (every = 1), 3 steps, reset, 2 steps -> the
