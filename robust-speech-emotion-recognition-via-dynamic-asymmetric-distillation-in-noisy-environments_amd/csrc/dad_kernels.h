@@ -210,7 +210,7 @@ __global__ void dad_optim(DadOptimArgs a);
 __global__ void dad_commit_kernel(dad_config cfg, const float* grad, float* dacp, float* tailf, float* losses_out);
 __global__ void dad_epoch_end_kernel(float* dacp, float beta, float one_m_beta);
 __global__ void dad_shadow_kernel(const float* student, const float* teacher, uint16_t* ws, uint16_t* wt, int f16);
-// helper-type drop-ins (DACPManager / ECDALoss, tail.hip; DataAugmentation, utils_abi.hip)
+// helper-type drop-ins (DACPManager / ECDALoss / DataAugmentation, utils_abi.hip)
 __global__ void dad_certainty_kernel(const float* probs, int B, int use_entropy, float* score, int64_t* pred);
 __global__ void dad_dacp_mask_kernel(dad_config cfg, const float* probs, int Bn, float* dacp, uint8_t* mask,
                                      float* score, int64_t* pred, float* wout);

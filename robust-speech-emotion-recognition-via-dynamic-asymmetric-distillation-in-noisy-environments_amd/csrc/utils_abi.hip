@@ -7,13 +7,15 @@
 //   ECDALoss.forward (+ its embedding gradients)        dad_ecda_loss         I/utils.py:510-652
 //
 // Each runs the device functions of the fused step (dad_common.h's augmentation draws,
-// tail.hip's certainty / thresholds / ECDA class blocks), so the helpers and the step agree.
+// tail_common.h's certainty and thresholds, tail_general.hip's ECDA class blocks: dad_ecda), so
+// the helpers and the step agree.  Their kernels stand before the operators that launch them.
 #include <string.h>
 
 #include <algorithm>
 
 #include "dad_common.h"
 #include "dad_kernels.h"
+#include "tail_common.h"
 
 namespace {
 
@@ -62,6 +64,102 @@ __global__ __launch_bounds__(256) void dad_augment_kernel(AugArgs a) {
 }
 
 }  // namespace
+
+// ------------------------------------------------------------- helper-type drop-ins
+// DACPManager.calculate_certainty_scores (I/utils.py:400-428): one thread per row of probs.
+__global__ __launch_bounds__(256) void dad_certainty_kernel(const float* probs, int B, int use_entropy, float* score,
+                                                            int64_t* pred) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const f32x4 v = reinterpret_cast<const f32x4*>(probs)[b];
+  const float q[4] = {v[0], v[1], v[2], v[3]};
+  float s;
+  int p;
+  certainty_from_probs(q, use_entropy != 0, s, p);
+  if (score) score[b] = s;
+  if (pred) pred[b] = p;
+}
+
+// DACPManager.calculate_mask (I/utils.py:449-507) on teacher probabilities, one workgroup:
+// the tail block's own thresholds (dacp_thresholds) and mask, then the state update the fused
+// step commits in dad_optim (tau EMA, epoch score sums and counts).  dacp = the 20-float state
+// (tau | Q | sums | counts | anchors).
+__global__ __launch_bounds__(TAIL_THREADS) void dad_dacp_mask_kernel(dad_config cfg, const float* probs, int Bn,
+                                                                      float* dacp, uint8_t* mask, float* score,
+                                                                      int64_t* pred, float* wout) {
+  DAD_GUARD_BLOCK(TAIL_THREADS);
+  __shared__ TailSmem T;
+  const int tid = threadIdx.x;
+  if (tid < 20) T.dstate[tid] = dacp[tid];
+  for (int b = tid; b < Bn; b += TAIL_THREADS) {
+    const f32x4 v = reinterpret_cast<const f32x4*>(probs)[b];
+    const float q[4] = {v[0], v[1], v[2], v[3]};
+    certainty_from_probs(q, cfg.use_entropy != 0, T.ss[b], T.sp[b]);
+  }
+  if (tid < DAD_C) T.ncls[tid] = 0;
+  __syncthreads();
+  float wc[DAD_C];
+  dacp_thresholds(cfg, Bn, T.ss, T.sp, T.srt, T.ncls, T.dstate, T.tau_new, wc, nullptr, nullptr);
+  double st4[4] = {0.0, 0.0, 0.0, 0.0}, ct4[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = tid; b < Bn; b += TAIL_THREADS) {
+    const int p = T.sp[b];
+    mask[b] = T.ss[b] >= T.tau_new[p] ? 1 : 0;
+    if (score) score[b] = T.ss[b];
+    if (pred) pred[b] = p;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      st4[c] += p == c ? (double)T.ss[b] : 0.0;
+      ct4[c] += p == c ? 1.0 : 0.0;
+    }
+  }
+  block_sum4_d(st4, T.dred4);
+  block_sum4_d(ct4, T.dred4);
+  if (tid < DAD_C) {
+    dacp[tid] = T.tau_new[tid];
+    dacp[8 + tid] += (float)st4[tid];
+    dacp[12 + tid] += (float)ct4[tid];
+    if (wout) wout[tid] = wc[tid];
+  }
+}
+
+// ECDALoss.forward (I/utils.py:565-652) on caller embeddings: stage them in the step's layout
+// (emb rows [clean | - | noisy], tail header + per-sample score / pred / mask) for dad_ecda.
+__global__ __launch_bounds__(256) void dad_ecda_prep_kernel(const float* clean, int B, const float* noisy, int Bn,
+                                                            const int64_t* noisy_labels, const uint8_t* noisy_mask,
+                                                            const float* noisy_scores, const float* class_weights,
+                                                            int nw, float* emb, float* tailf, uint32_t* eflag) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t nc = (size_t)B * DAD_H, nn = (size_t)Bn * DAD_H;
+  if (i < nc) emb[i] = clean[i];
+  if (i < nn) emb[(size_t)(B + Bn) * DAD_H + i] = noisy[i];
+  if (i < DAD_TAIL_HDR) {
+    float v = 0.0f;
+    if (i >= DAD_T_W && i < DAD_T_W + DAD_C) v = (int)(i - DAD_T_W) < nw ? class_weights[i - DAD_T_W] : 1.0f;
+    if (i == DAD_T_ECDA_ON) v = 1.0f;
+    tailf[i] = v;
+  }
+  if (i < (size_t)Bn) {
+    tailf[DAD_TAIL_HDR + i] = noisy_scores[i];
+    tailf[DAD_TAIL_HDR + Bn + i] = (float)noisy_labels[i];
+    tailf[DAD_TAIL_HDR + 2 * Bn + i] = noisy_mask[i] ? 1.0f : 0.0f;
+  }
+  if (i < (size_t)(B + Bn)) eflag[i] = 0u;
+}
+
+// loss = sum of the per-class terms (class-aware: ((t0 + t1) + t2) + t3, the reference's
+// accumulation order; global MMD: t0), grads = the member rows dad_ecda wrote, zero elsewhere
+__global__ __launch_bounds__(256) void dad_ecda_finish_kernel(int B, int Bn, const float* tailf, const float* ge,
+                                                              const uint32_t* eflag, float* loss, float* gclean,
+                                                              float* gnoisy) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t nc = (size_t)B * DAD_H, nn = (size_t)Bn * DAD_H;
+  if (i == 0 && loss) {
+    const float* t = tailf + DAD_T_ECDA_TERM;
+    *loss = ((t[0] + t[1]) + t[2]) + t[3];
+  }
+  if (gclean && i < nc) gclean[i] = eflag[i / DAD_H] ? ge[i] : 0.0f;
+  if (gnoisy && i < nn) gnoisy[i] = eflag[B + i / DAD_H] ? ge[nc + i] : 0.0f;
+}
 
 extern "C" {
 

@@ -184,7 +184,9 @@ def test_general_tail_kernel_switch_matches_wave_centric():
     """DAD_TAIL_W=0 (read once per process) selects the general tail + ECDA launch for every batch;
     in a subprocess it reproduces the wave-centric launch's losses, mask and gradient on a
     golden replay (the switch has no other coverage: the default takes the wave-centric kernel
-    for batches of at most 64 per side)."""
+    for batches of at most 64 per side).  The mask, the DACP class weights and the thresholds
+    before and after the step are equal bit for bit: both launches call one definition of the
+    threshold arithmetic (dacp_class_threshold, csrc/tail_common.h)."""
     here = os.path.dirname(os.path.abspath(__file__))
     code = ("import sys, json; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
             "import numpy as np, goldens, gpu_harness as gh\n"
@@ -195,7 +197,9 @@ def test_general_tail_kernel_switch_matches_wave_centric():
             "    gh.load_state(step, goldens.state(spec, s))\n"
             "    o = gh.run_step(step, goldens.step_inputs(spec, s), epoch, lr=float(d['s%%d_lr' %% s]))\n"
             "    out['s%%d' %% s] = [o['total_loss'], o['ecda_loss'], o['consistency_loss'],\n"
-            "                      [float(x) for x in o['mask']], float(np.linalg.norm(o['grads'][0]))]\n"
+            "                      [float(x) for x in o['mask']], float(np.linalg.norm(o['grads'][0])),\n"
+            "                      [float(x) for x in o['w']], [float(x) for x in o['tau_before']],\n"
+            "                      [float(x) for x in o['tau_after']]]\n"
             "print('RESULT' + json.dumps(out))\n") % (here, os.path.dirname(here))
     res = {}
     for mode in ("1", "0"):
@@ -209,6 +213,8 @@ def test_general_tail_kernel_switch_matches_wave_centric():
     for s in res["1"]:
         a, b = res["1"][s], res["0"][s]
         assert a[3] == b[3], (s, "mask")
+        for i, what in ((5, "w"), (6, "tau_before"), (7, "tau_after")):
+            assert len(a[i]) == 4 and a[i] == b[i], (s, what, a[i], b[i])
         for i in (0, 1, 2, 4):
             assert abs(a[i] - b[i]) <= 1e-4 * max(1.0, abs(b[i])), (s, i, a[i], b[i])
 

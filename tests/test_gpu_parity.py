@@ -264,7 +264,7 @@ def test_train_step_shim_with_reference_loop_body():
 @pytest.mark.parametrize("class_aware,B", [(True, 200), (False, 96), (True, 64), (False, 64)],
                          ids=["class_aware", "global_mmd", "class_aware_b64", "global_mmd_b64"])
 def test_large_member_sets_match_oracle(class_aware, B, prec):
-    """Large member sets: beyond the LDS-staged size (ECDA_NZ = 80 rows in csrc/tail.hip) the
+    """Large member sets: beyond the LDS-staged size (ECDA_NZ = 80 rows in csrc/tail_general.hip) the
     member rows and the distance matrix go through the global-memory path of dad_tail_ecda's
     class blocks, and the DACP ranks span several 512-thread rounds (B = 200 / 96, no register
     prefetch).  B = 64: the prefetch path (every row in registers at entry) with one class

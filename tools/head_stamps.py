@@ -1,5 +1,6 @@
-"""Diagnostic: dad_tail_ecda phase timeline (tail block and ECDA class blocks) (build variant 'stamps', -DDAD_PROBE_STAMPS;
-never the product library).  Runs bench-shaped steps and prints the last step's phases."""
+"""Diagnostic: dad_tail_ecda_w phase timeline (tail block and ECDA class blocks) (build variant 'stamps',
+-DDAD_PROBE_STAMPS; never the product library).  Runs bench-shaped steps and prints the last step's phases.
+Only the wave-centric launch (csrc/tail_w.hip) carries stamp points; slots it does not set are not printed."""
 import ctypes
 import os
 import sys
@@ -21,7 +22,7 @@ def main():
     P = bench.init_model_weights(model, seed=0)
     step = PKG.DADStep(model, flavor="iemocap", precision=os.environ.get("STAMP_PREC", "fp16"), rng="counter", seed=1)
     data = bench.make_batches(P, 2, B, T, seed=17, device=torch.device("cuda"))
-    S = 32  # slots per ECDA class (tail.hip ECDA_SLOTS)
+    S = 32  # slots per ECDA class (tail_w.hip ECDA_SLOTS)
     L = PKG.lib()
     reps = int(os.environ.get("STAMP_REPS", "15"))
     raw = []

@@ -14,7 +14,7 @@ os.environ.setdefault("DAD_LIB_VARIANT", "stamps")
 import bench  # noqa: E402
 
 PKG = bench.PKG
-NB = 4   # class blocks of dad_tail_ecda_w (tail.hip TW_CB)
+NB = 4   # class blocks of dad_tail_ecda_w (tail_w.hip: one per class, DAD_C)
 
 
 def main():
@@ -24,7 +24,7 @@ def main():
     step = PKG.DADStep(model, flavor="iemocap", precision=os.environ.get("STAMP_PREC", "fp16"), rng="counter", seed=1)
     data = bench.make_batches(P, 2, B, T, seed=int(os.environ.get("STAMP_SEED", "17")), device=torch.device("cuda"),
                               random_labels=os.environ.get("STAMP_RANDLAB") == "1")
-    S = 32  # slots per ECDA class (tail.hip ECDA_SLOTS)
+    S = 32  # slots per ECDA class (tail_w.hip ECDA_SLOTS)
     L = PKG.lib()
     reps = int(os.environ.get("STAMP_REPS", "15"))
     sleep = int(os.environ.get("STAMP_SLEEP", "0"))     # spin cycles queued ahead of each burst (0: none)
