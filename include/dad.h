@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DAD_ABI_VERSION 9
+#define DAD_ABI_VERSION 10
 
 /* error codes (besides hipError_t values) */
 #define DAD_OK 0
@@ -130,10 +130,10 @@ typedef struct dad_config {
 
 /* One clean + one noisy collated batch (I/dataload_noisy.py:124-129 format). */
 typedef struct dad_batch {
-  const float* xc;              /* [B][T][768] clean features */
+  const void* xc;               /* [B][T][768] clean features (f32; store mode: rows of xc_dtype) */
   const uint8_t* mc;            /* [B][T] padding mask, 1 = pad */
   const int64_t* yc;            /* [B] clean labels */
-  const float* xn;              /* [Bn][Tn][768] noisy features */
+  const void* xn;               /* [Bn][Tn][768] noisy features (f32; store mode: rows of xn_dtype) */
   const uint8_t* mn;            /* [Bn][Tn] */
   /* DAD_RNG_EXPLICIT only (parity mode; NULL otherwise): the reference's six draws */
   const float* nw;              /* [Bn][Tn][768] randn for weak aug */
@@ -153,6 +153,14 @@ typedef struct dad_batch {
   const int32_t* lenc;          /* [B] its frame count (rows >= it are padding) */
   const int64_t* rown;          /* [Bn] */
   const int32_t* lenn;          /* [Bn] */
+  /* ABI 10: the element type of the store rows, DAD_STORE_F32 (0) / DAD_STORE_F16 / DAD_STORE_BF16, of the
+   * clean store (with rowc) and the noisy store (with rown); the two stores may differ.  FP16 / BF16 steps
+   * read 16-bit rows in place wherever they prepare rows (dad_step, dad_step_encode, dad_step_compute,
+   * dad_step_backward_ahead[_split] for the next batch, dad_step_prepare_rows): each value is widened
+   * exactly to f32 and then treated as an f32 store row (rows of the operands' own type are copied as
+   * bytes), so a 16-bit store gives the results of its widened f32 copy.  FP32 steps: DAD_E_UNSUPPORTED.
+   * A padded batch (rowc / rown NULL) is f32: a non-zero value there is DAD_E_ARG. */
+  int32_t xc_dtype, xn_dtype;
 } dad_batch;
 
 /* Persistent training state, all caller-owned device buffers. */
@@ -172,7 +180,7 @@ typedef struct dad_state {
 } dad_state;
 
 /* --- sizing ------------------------------------------------------------------------ */
-/* DAD_ABI_VERSION the library was built with (ABI 9; 8 lacked dad_step_plan, 7 dad_eval_split, 6 dad_timing_reset): a binding compares it with the header's
+/* DAD_ABI_VERSION the library was built with (ABI 10; 9 lacked dad_batch.xc_dtype / xn_dtype, 8 dad_step_plan, 7 dad_eval_split, 6 dad_timing_reset): a binding compares it with the header's
  * value when it loads the library, so a stale build fails at load instead of at a call. */
 int dad_abi_version(void);
 size_t dad_param_count(void);
@@ -241,7 +249,10 @@ int dad_step_prepare_rows(const dad_config* cfg, const dad_batch* batch, void* w
  * the step itself enqueues from -- when its backward is dad_step_backward_ahead_split(.., next_cfg,
  * next_batch, defer, ..) (next_cfg = next_batch = NULL, defer = 0: dad_step_backward).  No device call;
  * the batch pointers are only tested for NULL, never followed.  A grid of 0 = that launch is not made;
- * kernel names are static strings.  Returns cfg's validation code, or DAD_E_ARG for cus < 2, out = NULL
+ * kernel names are static strings; dad_tail_ecda_w, dad_wgrad_direct[_f16]_cps (and the standalone dad_prep)
+ * also stand for their `_s16` siblings, the same kernels with the row loads in an fp16 / bf16 store's type,
+ * which the step launches in their place, with the same grids, when the rows that launch prepares lie in a
+ * 16-bit store (ABI 10).  Returns cfg's validation code, or DAD_E_ARG for cus < 2, out = NULL
  * or defer bits outside DAD_PREP_*; a next step that does not qualify for preparation ahead is no
  * error (prepped = 0).  Diagnostics and tests. */
 typedef struct dad_step_plan_info {

@@ -10,7 +10,7 @@ from . import _build
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 
-DAD_ABI_VERSION = 9        # dad.h DAD_ABI_VERSION this binding mirrors
+DAD_ABI_VERSION = 10       # dad.h DAD_ABI_VERSION this binding mirrors
 DAD_NPARAM = 256 * 768 + 256 + 4 * 256 + 4
 DAD_GRAD_EXTRA = 16
 DAD_GRAD_FLOATS = DAD_NPARAM + DAD_GRAD_EXTRA
@@ -21,6 +21,8 @@ PREC_FP32, PREC_BF16, PREC_FP16 = 0, 1, 2
 DRAW_WEAK, DRAW_STRONG, DRAW_FEAT_KEEP, DRAW_TSTART, DRAW_KEEP1, DRAW_KEEP2 = range(1, 7)
 RNG_EXPLICIT, RNG_COUNTER = 0, 1
 PREP_CLEAN, PREP_NOISY = 1, 2     # dad.h DAD_PREP_* (dad_step_backward_ahead_split / dad_step_prepare_rows)
+STORE_F32, STORE_F16, STORE_BF16 = 0, 1, 2   # dad.h DAD_STORE_* (dad_collate, dad_batch.xc_dtype / xn_dtype)
+E_ARG, E_SHAPE, E_COMM, E_UNSUPPORTED = 1001, 1002, 1003, 1004   # dad.h DAD_E_*
 
 # tail header slots (dad.h DAD_T_*)
 T_TOTAL, T_CE, T_KL, T_ECDA, T_SCL, T_MSUM, T_CLIPNORM, T_CLIPCOEF = range(8)
@@ -63,9 +65,10 @@ class DadConfig(ctypes.Structure):
 
 
 class DadBatch(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in
-                ("xc", "mc", "yc", "xn", "mn", "nw", "ns", "u", "start", "keep1", "keep2",
-                 "rowc", "lenc", "rown", "lenn")]
+    _fields_ = ([(n, ctypes.c_void_p) for n in
+                 ("xc", "mc", "yc", "xn", "mn", "nw", "ns", "u", "start", "keep1", "keep2",
+                  "rowc", "lenc", "rown", "lenn")]
+                + [("xc_dtype", ctypes.c_int32), ("xn_dtype", ctypes.c_int32)])   # STORE_* of the store rows
 
 
 class DadState(ctypes.Structure):

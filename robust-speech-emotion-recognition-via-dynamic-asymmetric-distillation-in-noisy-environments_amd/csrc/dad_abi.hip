@@ -22,7 +22,8 @@ int launch_prep(const DadPrepArgs& p, hipStream_t stream) {
   int cus = 0;
   const int rc = device_cus(&cus);
   if (rc) return rc;
-  hipLaunchKernelGGL(dad_prep, dim3(prep_grid_of(cus)), dim3(DAD_PREP_THREADS), 0, stream, p);
+  hipLaunchKernelGGL(dad_prep_s16_needed(p) ? dad_prep_s16 : dad_prep, dim3(prep_grid_of(cus)), dim3(DAD_PREP_THREADS), 0,
+                     stream, p);
   DAD_TRY(hipGetLastError());
   return DAD_OK;
 }
@@ -42,6 +43,7 @@ DadPrepArgs prep_args(const dad_config* cfg, const dad_batch* bt, uint16_t* x16)
   p.clean = 1;
   p.xc = bt->xc; p.xn = bt->xn;
   p.src = store_rows_of(bt);
+  p.src_types = bt->xc_dtype | (bt->xn_dtype << 8);   // (check_batch_dtypes: F32 for a padded batch)
   if (cfg->rng_mode == DAD_RNG_EXPLICIT) { p.nw = bt->nw; p.ns = bt->ns; p.u = bt->u; p.start = bt->start; }
   p.key_weak = k.weak; p.key_strong = k.strong; p.key_feat = k.feat; p.key_tstart = k.tstart;
   p.weak_std = cfg->weak_std; p.strong_std = cfg->strong_std; p.feat_p = cfg->feat_p;
@@ -61,7 +63,15 @@ int check_step_args(const dad_config* cfg, const dad_batch* bt, const dad_state*
   const bool explicit_rng = cfg->rng_mode == DAD_RNG_EXPLICIT;
   if (explicit_rng && cfg->p_drop > 0.0f && (!bt->keep1 || (!cfg->warmup && !bt->keep2))) return DAD_E_ARG;
   if (explicit_rng && !cfg->warmup && !has_explicit_draws(bt)) return DAD_E_ARG;
-  return rows_paired(bt) ? DAD_OK : DAD_E_ARG;
+  if (!rows_paired(bt)) return DAD_E_ARG;
+  return check_batch_dtypes(cfg, bt);
+}
+
+// the next batch a step may prepare (or NULL): one whose row types the step cannot read is an error,
+// not a batch left to its own step
+int check_next_batch(const dad_config* ncfg, const dad_batch* nbt) {
+  if (!ncfg || !nbt || check_cfg(ncfg) != DAD_OK) return DAD_OK;
+  return check_batch_dtypes(ncfg, nbt);
 }
 
 // p restricted to `parts` (DAD_PREP_*) of its set
@@ -146,6 +156,8 @@ int dad_step_plan(const dad_config* cfg, const dad_config* next_cfg, const dad_b
   const int rc = check_cfg(cfg);
   if (rc) return rc;
   if (cus < 2 || !out || (defer & ~(DAD_PREP_CLEAN | DAD_PREP_NOISY)) != 0) return DAD_E_ARG;
+  const int nrc = check_next_batch(next_cfg, next_batch);
+  if (nrc) return nrc;
   const StepPlan p = plan_step(cfg, next_cfg, next_batch, defer, cus);
   if (p.encode_rc) return p.encode_rc;
   *out = dad_step_plan_info{p.splits, p.max_splits, p.prep_grid, p.encode_grid, p.ws_nt, p.ws_ns, p.pool_grid,
@@ -174,6 +186,8 @@ static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const
   if (prepped) *prepped = 0;
   if (pending) *pending = 0;
   int rc = check_step_args(cfg, bt, st, workspace);
+  if (rc) return rc;
+  rc = check_next_batch(ncfg, nbt);
   if (rc) return rc;
   int cus = 0;
   rc = device_cus(&cus);
@@ -210,7 +224,9 @@ static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const
     memset(&ea, 0, sizeof(ea));
     ea.g = G; ea.warmup = cfg->warmup;
     ea.mask_len = cfg->mask_len; ea.start_hi = cfg->start_hi;
-    ea.xc = bt->xc; ea.mc = bt->mc; ea.xn = bt->xn; ea.mn = bt->mn; ea.src = src;
+    // (the FP32 encoder reads the rows, f32 by check_batch_dtypes; the 16-bit ones read the prepared set)
+    ea.xc = static_cast<const float*>(bt->xc); ea.mc = bt->mc; ea.xn = static_cast<const float*>(bt->xn); ea.mn = bt->mn;
+    ea.src = src;
     ea.w1_student = st->student + DAD_OFF_W1; ea.b1_student = st->student + DAD_OFF_B1;
     ea.w1_teacher = st->teacher + DAD_OFF_W1; ea.b1_teacher = st->teacher + DAD_OFF_B1;
     ea.w1h_student = st->w1bf_student;
@@ -225,7 +241,9 @@ static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const
     tk_begin();
     tk_mark(TK_E0, stream);
     if (plan.prep_grid) {
-      hipLaunchKernelGGL(dad_prep, dim3(plan.prep_grid), dim3(DAD_PREP_THREADS), 0, stream, prep_args(cfg, bt, xs16));
+      const DadPrepArgs own = prep_args(cfg, bt, xs16);
+      hipLaunchKernelGGL(dad_prep_s16_needed(own) ? dad_prep_s16 : dad_prep, dim3(plan.prep_grid), dim3(DAD_PREP_THREADS),
+                         0, stream, own);
       DAD_TRY(hipGetLastError());
     }
     const EncodeLaunch& enc = kEncodeLaunch[plan.encode - K_ENCODE_F32];
@@ -288,7 +306,10 @@ static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const
   switch (plan.tail) {
     case K_TAIL: hipLaunchKernelGGL(dad_tail, tgrid, tblock, 0, stream, ta); break;
     case K_TAIL_ECDA: hipLaunchKernelGGL(dad_tail_ecda, tgrid, tblock, 0, stream, ta, ca); break;
-    default: hipLaunchKernelGGL(dad_tail_ecda_w, tgrid, tblock, 0, stream, ta, ca, pp, pa); break;
+    default:   // (the `_s16` sibling when the rows it prepares lie in a 16-bit store, dad_kernels.h)
+      hipLaunchKernelGGL(pp.x16 && dad_prep_s16_needed(pp) ? dad_tail_ecda_w_s16 : dad_tail_ecda_w, tgrid, tblock, 0,
+                         stream, ta, ca, pp, pa);
+      break;
   }
   DAD_TRY(hipGetLastError());
   tk_mark(TK_TAIL, stream);
@@ -299,7 +320,7 @@ static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const
   memset(&wa, 0, sizeof(wa));
   wa.g = G; wa.warmup = cfg->warmup;
   wa.mask_len = cfg->mask_len; wa.start_hi = cfg->start_hi;
-  wa.xc = bt->xc; wa.xn = bt->xn; wa.src = src;
+  wa.xc = static_cast<const float*>(bt->xc); wa.xn = static_cast<const float*>(bt->xn); wa.src = src;   // (FP32 only)
   if (explicit_rng) { wa.ns = bt->ns; wa.u = bt->u; wa.start = bt->start; }
   wa.key_strong = k.strong; wa.key_feat = k.feat; wa.key_tstart = k.tstart;
   wa.strong_std = cfg->strong_std; wa.feat_p = cfg->feat_p;
@@ -320,7 +341,12 @@ static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const
   ra.pool_abort = plan.pool_grid ? nullptr : pool_ready + DAD_POOL_ABORT;
   ra.splits = plan.splits; ra.wpart = wa.wpart;
   const WgradLaunch& wg = kWgradLaunch[plan.wgrad - K_WGRAD_F32];
-  if (wg.cp) hipLaunchKernelGGL(wg.cp, dim3(plan.wgrad_grid), dim3(wg.threads), 0, stream, wa, ra, pcw);
+  if (wg.cp) {
+    auto cp = wg.cp;
+    if (plan.wgrad_store && pcw.xc_type() != DAD_STORE_F32)
+      cp = cfg->precision == DAD_PREC_FP16 ? dad_wgrad_direct_f16_cps_s16 : dad_wgrad_direct_cps_s16;
+    hipLaunchKernelGGL(cp, dim3(plan.wgrad_grid), dim3(wg.threads), 0, stream, wa, ra, pcw);
+  }
   else hipLaunchKernelGGL(wg.kernel, dim3(plan.wgrad_grid), dim3(wg.threads), 0, stream, wa, ra);
   DAD_TRY(hipGetLastError());
   tk_mark(TK_WGRAD, stream);
@@ -373,6 +399,8 @@ int dad_step_prepare_rows(const dad_config* cfg, const dad_batch* bt, void* work
   if ((parts & DAD_PREP_NOISY) && (!bt->xn || (cfg->rng_mode == DAD_RNG_EXPLICIT && !has_explicit_draws(bt))))
     return DAD_E_ARG;
   if (!rows_paired(bt)) return DAD_E_ARG;
+  const int drc = check_batch_dtypes(cfg, bt);
+  if (drc) return drc;
   if (parts == 0) return DAD_OK;
   const DadWs L = dad_ws_layout(geom_of(cfg), max_splits_of(cfg), cfg->precision);
   DadPrepArgs p = prep_args(cfg, bt, ws_ptr<uint16_t>(workspace, L.xs16 + (cfg->counter & 1u) * L.x16set));

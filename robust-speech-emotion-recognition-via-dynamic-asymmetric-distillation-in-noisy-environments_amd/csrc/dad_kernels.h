@@ -94,12 +94,17 @@ struct DadPrepArgs {
   DadGeom g;
   int warmup, mask_len, start_hi, f16;
   int clean;                // 1: also the clean rows (else the encoder converts them itself)
-  const float* xc; const float* xn;
+  int src_types;            // DAD_STORE_* of the clean (bits 0-7) and noisy (bits 8-15) source rows, F32 for a padded
+                            // batch (xc_type / xn_type); read by the `_s16` kernels only.  (It fills what was
+                            // padding before the pointers: every other field sits where it sat.)
+  const void* xc; const void* xn;   // rows of type xc_type() / xn_type()
   DadStoreRows src;
   const float* nw; const float* ns; const float* u; const int64_t* start;   // explicit draws, or NULL
   uint32_t key_weak, key_strong, key_feat, key_tstart;
   float weak_std, strong_std, feat_p;
   uint16_t* x16;            // the set; NULL: nothing to prepare (tail launch without a next batch)
+  __host__ __device__ int xc_type() const { return src_types & 0xff; }
+  __host__ __device__ int xn_type() const { return (src_types >> 8) & 0xff; }
 };
 
 
@@ -187,6 +192,15 @@ __global__ void dad_encode_wp(DadEncodeArgs a);                // bf16 operands 
 __global__ void dad_encode_wp_f16(DadEncodeArgs a);            // fp16 operands from a prepared set
 #define DAD_PREP_THREADS 256
 __global__ void dad_prep(DadPrepArgs a);                       // one prepared set, standalone
+// The `_s16` siblings (dad_prep_s16, dad_tail_ecda_w_s16, dad_wgrad_direct[_f16]_cps_s16): the same kernels
+// with the row loads in an fp16 / bf16 store's type, launched in their place when the rows a launch
+// prepares come from such a store (dad_prep_s16_needed).  The step plan names the f32 kernel for both.
+__global__ void dad_prep_s16(DadPrepArgs a);
+// a part of p's set that p prepares is read from a 16-bit store
+static inline bool dad_prep_s16_needed(const DadPrepArgs& p) {
+  const bool noisy = !p.warmup && p.g.Bn > 0;
+  return (p.clean && p.xc_type() != DAD_STORE_F32) || (noisy && p.xn_type() != DAD_STORE_F32);
+}
 __global__ void dad_pool(DadPoolArgs a);
 __global__ void dad_tail(DadTailArgs a);
 __global__ void dad_ecda(DadEcdaArgs a);
@@ -194,6 +208,7 @@ __global__ void dad_tail_ecda(DadTailArgs ta, DadEcdaArgs ca);
 // B, Bn <= 64, class-aware; blocks > DAD_C pool the step's embeddings first (pl.ready != NULL)
 // and then prepare the next step's set (pa.x16 != NULL)
 __global__ void dad_tail_ecda_w(DadTailArgs ta, DadEcdaArgs ca, DadPrepArgs pa, DadPoolArgs pl);
+__global__ void dad_tail_ecda_w_s16(DadTailArgs ta, DadEcdaArgs ca, DadPrepArgs pa, DadPoolArgs pl);
 __global__ void dad_wgrad_f32(DadWgradArgs a, DadReduceArgs r);   // r: the fused step's dL/de sources (gzb) or zeroed
 __global__ void dad_wgrad_direct(DadWgradArgs a, DadReduceArgs r);       // bf16 operands
 __global__ void dad_wgrad_direct_f16(DadWgradArgs a, DadReduceArgs r);   // fp16 operands
@@ -203,6 +218,8 @@ __global__ void dad_wgrad_direct_f16_cp(DadWgradArgs a, DadReduceArgs r, DadPrep
 // store-batch variants (the next batch's clean rows gathered from a FeatureStore, Bc <= 64)
 __global__ void dad_wgrad_direct_cps(DadWgradArgs a, DadReduceArgs r, DadPrepArgs pc);
 __global__ void dad_wgrad_direct_f16_cps(DadWgradArgs a, DadReduceArgs r, DadPrepArgs pc);
+__global__ void dad_wgrad_direct_cps_s16(DadWgradArgs a, DadReduceArgs r, DadPrepArgs pc);
+__global__ void dad_wgrad_direct_f16_cps_s16(DadWgradArgs a, DadReduceArgs r, DadPrepArgs pc);
 __global__ void dad_reduce(DadReduceArgs a);
 __global__ void dad_reduce_w(DadReduceArgs a);
 __global__ void dad_norm(float* grad, float* normpart, float inv_world);

@@ -12,8 +12,9 @@
 // Output: one prepared set [clean Bc*Tc | strong Bn*Tn | weak Bn*Tn][768] of 16-bit rows in the
 // padded layout (row b*T + t), whatever the source mode.  The strong and clean parts are also the
 // weight gradient's operand.  The step prepares all three parts (a.clean = 1; 206 MB of HBM
-// traffic at B=64, T=300: 118 MB of fp32 rows read, 88.5 MB of 16-bit rows written); a.clean = 0
-// (noisy rows only) is kept for callers whose clean rows are converted elsewhere.
+// traffic at B=64, T=300: 118 MB of fp32 rows read, 88.5 MB of 16-bit rows written; from fp16 / bf16
+// store rows, read in place (DadSrc below), 59 MB read: 147.5 MB); a.clean = 0 (noisy rows only) is
+// kept for callers whose clean rows are converted elsewhere.
 //
 // One wave per row; lane l owns columns 256k + 4l .. +3 (k = 0..2): the element pairs the fused
 // encoder converted per lane, so the counter RNG draws the same values (pair (row*768 + d) / 2 of
@@ -50,6 +51,43 @@ __device__ __forceinline__ void dad_prep_st(char* p, uint2 v) {
   else *reinterpret_cast<uint2*>(p) = v;
 }
 
+// Source element types of the raw feature rows: float (padded batches, f32 stores) or the 16-bit
+// store types (dad_batch.xc_dtype / xn_dtype: _Float16 = DAD_STORE_F16, __bf16 = DAD_STORE_BF16),
+// read in place.  raw = the lane's four columns of one piece as loaded: 16 B of a 3072-B f32 row,
+// 8 B of a 1536-B 16-bit row (byte offset 512k + 8 lane); widened exactly to f32 only where the
+// row is converted, so a row in flight holds 6 VGPRs instead of 12.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <typename S> struct DadSrc { typedef u32x2 raw; };
+template <> struct DadSrc<float> { typedef f32x4 raw; };
+template <typename S>
+__device__ __forceinline__ f32x4 dad_src_widen(typename DadSrc<S>::raw r) {
+  if constexpr (sizeof(S) == 4) {
+    return r;
+  } else if constexpr (__is_same(S, _Float16)) {
+    return __builtin_convertvector(__builtin_bit_cast(f16x4, r), f32x4);
+  } else {   // bf16: the high half of the f32 with the same value
+    return f32x4{__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xffff0000u), __uint_as_float(r[1] << 16),
+                 __uint_as_float(r[1] & 0xffff0000u)};
+  }
+}
+// the piece as 16-bit operands (fp16 if F16, else bf16).  A store of the operands' own type is copied
+// as bytes (widening then rounding is the identity for finite values); any other pair goes through f32.
+template <bool F16, typename S>
+__device__ __forceinline__ uint2 dad_src_pack(typename DadSrc<S>::raw r) {
+  if constexpr (__is_same(S, _Float16) == F16 && sizeof(S) == 2) {
+    return uint2{r[0], r[1]};
+  } else {
+    const f32x4 v = dad_src_widen<S>(r);
+    return uint2{dad_pack2<F16>(v[0], v[1]), dad_pack2<F16>(v[2], v[3])};
+  }
+}
+// the piece at x (the lane's four columns of it), non-temporal
+template <typename S>
+__device__ __forceinline__ typename DadSrc<S>::raw dad_src_load(const S* x) {
+  return __builtin_nontemporal_load(reinterpret_cast<const typename DadSrc<S>::raw*>(x));
+}
+
 template <int NOISE>
 __device__ __forceinline__ int dad_prep_tstart(const DadPrepArgs& a, int b) {
   if (NOISE) return (int)a.start[b];
@@ -61,12 +99,15 @@ __device__ __forceinline__ int dad_prep_tstart(const DadPrepArgs& a, int b) {
 // lane b of two registers, loaded once, so a row's source is a readlane instead of two dependent
 // global loads per row (dad_src_row): the tail launch's noisy preparation of a store batch took
 // 40.2 us against 29.8 for a padded batch (events, one box).
-template <int NOISE, bool F16, int R, bool STOREN>
-__device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, int nwaves, int lane) {
+// S: the source element type of every row this call prepares; clean / noisy: the parts of the set it
+// prepares (dad_prep_dispatch: a.clean and every noisy row, unless the two parts differ in type).
+template <int NOISE, bool F16, int R, bool STOREN, typename S = float>
+__device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, int nwaves, int lane, int clean,
+                                              bool noisy_part) {
   const DadGeom& G = a.g;
   const int Nc = G.Bc * G.Tc;
   const int Nn = a.warmup ? 0 : G.Bn * G.Tn;
-  const int N = Nc + Nn;
+  const int N = noisy_part ? Nc + Nn : Nc;
   uint16_t* const oc = a.x16;
   uint16_t* const os = a.x16 + (size_t)Nc * DAD_D;
   uint16_t* const ow = os + (size_t)Nn * DAD_D;
@@ -85,8 +126,8 @@ __device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, in
   for (int k = 0; k < 3; ++k)
 #pragma unroll
     for (int e = 0; e < 4; ++e) kp[k][e] = dad_feat_keep(a.u, a.key_feat, 256 * k + 4 * lane + e, a.feat_p);
-  for (int base = (a.clean ? 0 : Nc) + wave; base < N; base += R * nwaves) {
-    f32x4 v[R][3];
+  for (int base = (clean ? 0 : Nc) + wave; base < N; base += R * nwaves) {
+    typename DadSrc<S>::raw v[R][3];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int u = min(base + r * nwaves, N - 1);
@@ -102,9 +143,9 @@ __device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, in
       } else {
         srow = dad_src_row(a.src, noisy, b, T, t);
       }
-      const float* x = (noisy ? a.xn : a.xc) + srow * DAD_D + 4 * lane;
+      const S* x = static_cast<const S*>(noisy ? a.xn : a.xc) + srow * DAD_D + 4 * lane;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) v[r][k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + 256 * k));
+      for (int k = 0; k < 3; ++k) v[r][k] = dad_src_load<S>(x + 256 * k);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -113,8 +154,7 @@ __device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, in
       if (u < Nc) {
         char* o = reinterpret_cast<char*>(oc + (size_t)u * DAD_D + 4 * lane);
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-          dad_prep_st<true>(o + 512 * k, uint2{dad_pack2<F16>(v[r][k][0], v[r][k][1]), dad_pack2<F16>(v[r][k][2], v[r][k][3])});
+        for (int k = 0; k < 3; ++k) dad_prep_st<true>(o + 512 * k, dad_src_pack<F16, S>(v[r][k]));
         continue;
       }
       const int un = u - Nc;
@@ -143,11 +183,12 @@ __device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, in
           ns = f32x4{z[4], z[5], z[6], z[7]};
         }
         // reference op order: x + std*N, then * feature mask, then temporal zero
+        const f32x4 x = dad_src_widen<S>(v[r][k]);
         f32x4 w, s;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          w[e] = v[r][k][e] + nw[e];
-          s[e] = (v[r][k][e] + ns[e]) * kp[k][e];
+          w[e] = x[e] + nw[e];
+          s[e] = (x[e] + ns[e]) * kp[k][e];
         }
         dad_prep_st<true>(o_w + 512 * k, uint2{dad_pack2<F16>(w[0], w[1]), dad_pack2<F16>(w[2], w[3])});
         const uint2 so = uint2{dad_pack2<F16>(s[0], s[1]), dad_pack2<F16>(s[2], s[3])};
@@ -158,21 +199,54 @@ __device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, in
 }
 
 // runtime dispatch on the set's precision and draw source (wave-uniform)
-template <int R, bool STOREN>
-__device__ __forceinline__ void dad_prep_dispatch_s(const DadPrepArgs& a, int wave, int nwaves, int lane) {
+template <int R, bool STOREN, typename S>
+__device__ __forceinline__ void dad_prep_dispatch_s(const DadPrepArgs& a, int wave, int nwaves, int lane, int clean,
+                                                    bool noisy) {
   const bool noise = a.nw != nullptr;
   if (a.f16) {
-    if (noise) dad_prep_rows<1, true, R, STOREN>(a, wave, nwaves, lane);
-    else dad_prep_rows<0, true, R, STOREN>(a, wave, nwaves, lane);
+    if (noise) dad_prep_rows<1, true, R, STOREN, S>(a, wave, nwaves, lane, clean, noisy);
+    else dad_prep_rows<0, true, R, STOREN, S>(a, wave, nwaves, lane, clean, noisy);
   } else {
-    if (noise) dad_prep_rows<1, false, R, STOREN>(a, wave, nwaves, lane);
-    else dad_prep_rows<0, false, R, STOREN>(a, wave, nwaves, lane);
+    if (noise) dad_prep_rows<1, false, R, STOREN, S>(a, wave, nwaves, lane, clean, noisy);
+    else dad_prep_rows<0, false, R, STOREN, S>(a, wave, nwaves, lane, clean, noisy);
   }
 }
-template <int R>
+template <int R, typename S>
+__device__ __forceinline__ void dad_prep_dispatch_t(const DadPrepArgs& a, int wave, int nwaves, int lane, int clean,
+                                                    bool noisy) {
+  if (a.src.rown != nullptr && a.g.Bn <= 64 && !a.warmup) dad_prep_dispatch_s<R, true, S>(a, wave, nwaves, lane, clean, noisy);
+  else dad_prep_dispatch_s<R, false, S>(a, wave, nwaves, lane, clean, noisy);
+}
+// ... and on the rows' source type (DAD_STORE_*; wave-uniform).  The clean and the noisy store may
+// differ in type: the clean rows then go first, in a pass of their own, and the noisy rows follow in
+// theirs, so no pass holds a load under a condition and the type pairs need no instantiations of
+// their own.
+template <int R, typename S>
+__device__ __forceinline__ void dad_prep_clean_pass(const DadPrepArgs& a, int wave, int nwaves, int lane) {
+  if (a.f16) dad_prep_rows<0, true, R, false, S>(a, wave, nwaves, lane, 1, false);
+  else dad_prep_rows<0, false, R, false, S>(a, wave, nwaves, lane, 1, false);
+}
+// S16 = false: every source row is f32 (padded batches and f32 stores; dad_prep, dad_tail_ecda_w).
+// S16 = true: the `_s16` siblings of those kernels, launched when a part of the set comes from an
+// fp16 / bf16 store (dad_prep_s16_needed); kernels of their own, so that the f32 kernels hold the f32
+// code alone and compile to what they did before the 16-bit stores.
+template <int R, bool S16 = false>
 __device__ __forceinline__ void dad_prep_dispatch(const DadPrepArgs& a, int wave, int nwaves, int lane) {
-  if (a.src.rown != nullptr && a.g.Bn <= 64 && !a.warmup) dad_prep_dispatch_s<R, true>(a, wave, nwaves, lane);
-  else dad_prep_dispatch_s<R, false>(a, wave, nwaves, lane);
+  if constexpr (!S16) {
+    dad_prep_dispatch_t<R, float>(a, wave, nwaves, lane, a.clean, true);
+  } else {
+    const bool has_noisy = !a.warmup && a.g.Bn > 0;
+    const int tn = has_noisy ? a.xn_type() : a.xc_type(), tc = a.clean ? a.xc_type() : tn;
+    if (tc != tn) {
+      if (tc == DAD_STORE_F16) dad_prep_clean_pass<R, _Float16>(a, wave, nwaves, lane);
+      else if (tc == DAD_STORE_BF16) dad_prep_clean_pass<R, __bf16>(a, wave, nwaves, lane);
+      else dad_prep_clean_pass<R, float>(a, wave, nwaves, lane);
+    }
+    const int clean = tc == tn ? a.clean : 0;
+    if (tn == DAD_STORE_F16) dad_prep_dispatch_t<R, _Float16>(a, wave, nwaves, lane, clean, true);
+    else if (tn == DAD_STORE_BF16) dad_prep_dispatch_t<R, __bf16>(a, wave, nwaves, lane, clean, true);
+    else dad_prep_dispatch_t<R, float>(a, wave, nwaves, lane, clean, true);
+  }
 }
 
 // One CLEAN row of a prepared set in two halves, for callers that interleave it with other work
@@ -210,23 +284,25 @@ __device__ __forceinline__ size_t dad_clean_src_row(const DadPrepArgs& a, int uc
   const int len = __builtin_amdgcn_readlane(sr.len, b);
   return (size_t)(base + (uint64_t)min(t, max(len, 1) - 1));   // dad_src_row's rule
 }
-template <bool STORE = false>
-__device__ __forceinline__ void dad_prep_clean_load(const DadPrepArgs& a, int u, int lane, f32x4 (&v)[3],
+// S: the clean rows' source type (a.xc_type(); the caller's compile-time copy, as F16 below)
+template <bool STORE = false, typename S = float>
+__device__ __forceinline__ void dad_prep_clean_load(const DadPrepArgs& a, int u, int lane,
+                                                    typename DadSrc<S>::raw (&v)[3],
                                                     const StoreRowsW& sr = StoreRowsW{}) {
   const int uc = min(u, a.g.Bc * a.g.Tc - 1);
-  const float* x = a.xc + dad_clean_src_row<STORE>(a, uc, sr) * DAD_D + 4 * lane;
+  const S* x = static_cast<const S*>(a.xc) + dad_clean_src_row<STORE>(a, uc, sr) * DAD_D + 4 * lane;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) v[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + 256 * k));
+  for (int k = 0; k < 3; ++k) v[k] = dad_src_load<S>(x + 256 * k);
 }
 // (a row past the end was loaded as the last row and is stored there again: the same bytes, so the
 // stores need no condition -- a conditional memory operation inside the caller's pipelined loop
 // would make hipcc drain the loads in flight where the paths merge)
 // F16: the set's precision (a.f16; the caller's compile-time copy, so no branch sits between stores)
-template <bool F16>
-__device__ __forceinline__ void dad_prep_clean_store(const DadPrepArgs& a, int u, int lane, const f32x4 (&v)[3]) {
+template <bool F16, typename S = float>
+__device__ __forceinline__ void dad_prep_clean_store(const DadPrepArgs& a, int u, int lane,
+                                                     const typename DadSrc<S>::raw (&v)[3]) {
   const int uc = min(u, a.g.Bc * a.g.Tc - 1);
   char* o = reinterpret_cast<char*>(a.x16 + (size_t)uc * DAD_D + 4 * lane);
 #pragma unroll
-  for (int k = 0; k < 3; ++k)
-    dad_prep_st<false>(o + 512 * k, uint2{dad_pack2<F16>(v[k][0], v[k][1]), dad_pack2<F16>(v[k][2], v[k][3])});
+  for (int k = 0; k < 3; ++k) dad_prep_st<false>(o + 512 * k, dad_src_pack<F16, S>(v[k]));
 }

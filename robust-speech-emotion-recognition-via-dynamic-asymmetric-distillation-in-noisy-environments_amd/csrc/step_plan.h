@@ -28,6 +28,17 @@ inline DadGeom geom_of(const dad_config* c) { return dad_geom(c->B, c->T, c->Bn,
 inline bool rows_paired(const dad_batch* b) {
   return (b->rowc == nullptr) == (b->lenc == nullptr) && (b->rown == nullptr) == (b->lenn == nullptr);
 }
+// The element types of a batch's feature rows (dad_batch.xc_dtype / xn_dtype): a padded batch is
+// f32; a 16-bit store is read in place by the 16-bit steps' row preparation only (the exact-f32
+// encoder and weight gradient read f32 rows).
+inline bool store_dtype_ok(int t) { return t == DAD_STORE_F32 || t == DAD_STORE_F16 || t == DAD_STORE_BF16; }
+inline int check_batch_dtypes(const dad_config* c, const dad_batch* b) {
+  if (!store_dtype_ok(b->xc_dtype) || !store_dtype_ok(b->xn_dtype)) return DAD_E_ARG;
+  if ((!b->rowc && b->xc_dtype != DAD_STORE_F32) || (!b->rown && b->xn_dtype != DAD_STORE_F32)) return DAD_E_ARG;
+  if ((b->xc_dtype != DAD_STORE_F32 || b->xn_dtype != DAD_STORE_F32) && !dad_prec16(c->precision))
+    return DAD_E_UNSUPPORTED;
+  return DAD_OK;
+}
 // DAD_RNG_EXPLICIT: the augmentation's four draws of a noisy batch
 inline bool has_explicit_draws(const dad_batch* b) { return b->nw && b->ns && b->u && b->start; }
 
@@ -143,6 +154,9 @@ inline bool can_prepare_ahead(const dad_config* cfg, int max_splits, const dad_c
   if (ncfg->B != cfg->B || ncfg->T != cfg->T || ncfg->Bn != cfg->Bn || ncfg->Tn != cfg->Tn) return false;
   if (((ncfg->counter ^ cfg->counter) & 1u) == 0) return false;
   if (max_splits_of(ncfg) != max_splits) return false;
+  // (a store of any DAD_STORE_* type qualifies: the preparation reads 16-bit rows in place; the callers
+  // report check_batch_dtypes' code for a batch it refuses)
+  if (check_batch_dtypes(ncfg, nbt) != DAD_OK) return false;
   if (!nbt->xc || !nbt->mc) return false;
   if (!ncfg->warmup && (!nbt->xn || !nbt->mn)) return false;
   if (ncfg->rng_mode == DAD_RNG_EXPLICIT && !ncfg->warmup && !has_explicit_draws(nbt)) return false;

@@ -975,8 +975,17 @@ __device__ __forceinline__ void ecda_block_w(const DadEcdaArgs& a, const DadTail
 // idle; it reads only the next batch and writes only the other prepared set, so it overlaps this
 // step's latency-bound tail and ECDA.  The tail and class blocks have the lowest block ids, so
 // they are dispatched first and never wait for a CU behind the preparation blocks.
-__global__ __launch_bounds__(TAIL_THREADS) void dad_tail_ecda_w(DadTailArgs ta, DadEcdaArgs ca, DadPrepArgs pa,
-                                                                  DadPoolArgs pl) {
+// tail_w_s16.hip compiles this file again as dad_tail_ecda_w_s16: the same launch with the preparation
+// reading rows of an fp16 / bf16 store (dad_prep_dispatch, S16).  A kernel and a unit of its own, so
+// that this one holds the f32 preparation alone and compiles to what it did before the 16-bit stores.
+#ifdef DAD_TAIL_W_S16
+#define TAIL_W_KERNEL dad_tail_ecda_w_s16
+#else
+#define TAIL_W_KERNEL dad_tail_ecda_w
+#define DAD_TAIL_W_S16 0
+#endif
+__global__ __launch_bounds__(TAIL_THREADS) void TAIL_W_KERNEL(DadTailArgs ta, DadEcdaArgs ca, DadPrepArgs pa,
+                                                                DadPoolArgs pl) {
   DAD_GUARD_BLOCK(TAIL_THREADS);
   __shared__ union UW {
     TailW t;
@@ -997,7 +1006,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void dad_tail_ecda_w(DadTailArgs ta, 
 #ifdef DAD_PROBE_STAMPS
     if ((threadIdx.x & 63) == 0 && xb < 256) prep_stamps[2 * (xb * kWaves + w)] = DAD_PROBE_WALL();
 #endif
-    dad_prep_dispatch<2>(pa, xb * kWaves + w, nx * kWaves, (int)threadIdx.x & 63);
+    dad_prep_dispatch<2, DAD_TAIL_W_S16>(pa, xb * kWaves + w, nx * kWaves, (int)threadIdx.x & 63);
 #ifdef DAD_PROBE_STAMPS
     if (threadIdx.x == 0) atomicMax(&ecda_stamps[DAD_C * ECDA_SLOTS + 15], (unsigned long long)DAD_PROBE_WALL());
     if ((threadIdx.x & 63) == 0 && xb < 256) prep_stamps[2 * (xb * kWaves + w) + 1] = DAD_PROBE_WALL();

@@ -530,27 +530,33 @@ __device__ __forceinline__ int wgd_f16_exp(float max_abs) {
 
 // dad_prep_clean_load / _store with the row's address in SGPRs (u is wave-uniform): a buffer
 // resource per row, the lane's column offset a loop-invariant register, the three 16-B / 8-B
-// pieces at immediate offsets; non-temporal loads as in dad_prep_clean_load
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-template <bool STORE>
-__device__ __forceinline__ void wgd_cp_load(const DadPrepArgs& a, int u, uint32_t loff, f32x4 (&v)[3],
+// pieces at immediate offsets; non-temporal loads as in dad_prep_clean_load.  S: the clean rows'
+// source type (DadSrc; a 16-bit store row is 1536 B, its pieces 8 B at 512 k + 8 lane)
+template <bool STORE, typename S>
+__device__ __forceinline__ void wgd_cp_load(const DadPrepArgs& a, int u, uint32_t loff, typename DadSrc<S>::raw (&v)[3],
                                             const StoreRowsW& sr) {
   const int uc = min(u, a.g.Bc * a.g.Tc - 1);
   const size_t srow = dad_clean_src_row<STORE>(a, uc, sr);
-  const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.xc + srow * DAD_D), (short)0, DAD_D * 4,
-                                                   0x00020000);
+  const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<S*>(static_cast<const S*>(a.xc) + srow * DAD_D), (short)0,
+                                                   DAD_D * (int)sizeof(S), 0x00020000);
 #pragma unroll
-  for (int k = 0; k < 3; ++k)
-    v[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, loff + 1024 * k, 0, 2));
+  for (int k = 0; k < 3; ++k) {
+    if constexpr (sizeof(S) == 4)
+      v[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, loff + 1024 * k, 0, 2));
+    else
+      v[k] = __builtin_amdgcn_raw_buffer_load_b64(r, loff + 512 * k, 0, 2);
+  }
 }
-template <bool F16>
-__device__ __forceinline__ void wgd_cp_store(const DadPrepArgs& a, int u, uint32_t soff, const f32x4 (&v)[3]) {
+template <bool F16, typename S>
+__device__ __forceinline__ void wgd_cp_store(const DadPrepArgs& a, int u, uint32_t soff,
+                                             const typename DadSrc<S>::raw (&v)[3]) {
   const int uc = min(u, a.g.Bc * a.g.Tc - 1);
   const auto r = __builtin_amdgcn_make_buffer_rsrc(a.x16 + (size_t)uc * DAD_D, (short)0, DAD_D * 2, 0x00020000);
 #pragma unroll
-  for (int k = 0; k < 3; ++k)
-    __builtin_amdgcn_raw_buffer_store_b64(u32x2{dad_pack2<F16>(v[k][0], v[k][1]), dad_pack2<F16>(v[k][2], v[k][3])}, r,
-                                          soff + 512 * k, 0, 0);
+  for (int k = 0; k < 3; ++k) {
+    const uint2 o = dad_src_pack<F16, S>(v[k]);
+    __builtin_amdgcn_raw_buffer_store_b64(u32x2{o.x, o.y}, r, soff + 512 * k, 0, 0);
+  }
 }
 
 // x-tile LDS buffers per slab group: a slab is staged two rounds before it is read, one barrier
@@ -562,8 +568,8 @@ constexpr int WGD_NBUF = 4;
 // the first round of each block of NB rounds and are converted and stored at the start of the next
 // block (an HBM miss under this load takes about as long as NB rounds); the rows left after the
 // loop follow it.  CP = 1: padded next batch; CP = 2: store batch (Bc <= 64), source rows through
-// the utterance table held in registers (StoreRowsW).
-template <bool F16, int CP>
+// the utterance table held in registers (StoreRowsW), rows of type SC (a 16-bit store is read in place).
+template <bool F16, int CP, typename SC = float>
 __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceArgs& ra, int s0, int s1, int dbase,
                                          float* outf, uint16_t* Xt, const uint4* lut, uint16_t* gs, float* red,
                                          const DadPrepArgs& pc, int gw, int GW) {
@@ -577,7 +583,8 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
 #pragma unroll
     for (int n = 0; n < 2; ++n) acc[m][n] = f32x16{};
   float unscale = 1.0f;   // FP16: 2^-s_h of row h = 64 wv + lane
-  const uint32_t cploff = (uint32_t)lane * 16u, cpsoff = (uint32_t)lane * 8u;   // CP: a row's lane columns
+  const uint32_t cploff = (uint32_t)lane * (4u * sizeof(SC)), cpsoff = (uint32_t)lane * 8u;   // CP: a row's lane columns
+  typedef typename DadSrc<SC>::raw CpRaw;
   for (int k = 0; DAD_PROBE_ON && k < 10; ++k)
     if (tid == 0 && blockIdx.x < 512) DAD_PROBE_SET(wgd_stamps, blockIdx.x * 10 + k, 0);
   const unsigned long long t0 = WGD_CLK();
@@ -739,9 +746,9 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
     int j = 1;
     int prow = gw;        // CP: this wave's next clean row of the next step
     const StoreRowsW srw = CP == 2 ? dad_store_rows_w(pc, lane) : StoreRowsW{};
-    f32x4 pv[2][3];
+    CpRaw pv[2][3];
     bool pending = false; // CP: rows prow - 2 GW, prow - GW loaded, not yet stored
-    f32x4 po[2][3];       // CP two blocks ahead: rows prow - 4 GW, prow - 3 GW (loaded two blocks ago)
+    CpRaw po[2][3];       // CP two blocks ahead: rows prow - 4 GW, prow - 3 GW (loaded two blocks ago)
     bool pend2 = false;
     for (; j + NB - 1 + SD < cntmin; j += NB) {   // every round stages slab j + k + SD < cntmin
 #pragma unroll
@@ -750,16 +757,16 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
           if (k == 0) {
             // the rows loaded two blocks (2 NB rounds) ago, then this block's two
             if (pend2) {
-              wgd_cp_store<F16>(pc, prow - 4 * GW, cpsoff, po[0]);
-              wgd_cp_store<F16>(pc, prow - 3 * GW, cpsoff, po[1]);
+              wgd_cp_store<F16, SC>(pc, prow - 4 * GW, cpsoff, po[0]);
+              wgd_cp_store<F16, SC>(pc, prow - 3 * GW, cpsoff, po[1]);
             }
 #pragma unroll
             for (int q = 0; q < 2; ++q)
 #pragma unroll
               for (int e = 0; e < 3; ++e) po[q][e] = pv[q][e];
             pend2 = pending;
-            wgd_cp_load<CP == 2>(pc, prow, cploff, pv[0], srw);
-            wgd_cp_load<CP == 2>(pc, prow + GW, cploff, pv[1], srw);
+            wgd_cp_load<CP == 2, SC>(pc, prow, cploff, pv[0], srw);
+            wgd_cp_load<CP == 2, SC>(pc, prow + GW, cploff, pv[1], srw);
             prow += 2 * GW;
             pending = true;
           }
@@ -774,25 +781,25 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
     if (nround - 1 < mine) wgd_mma<F16>(F, acc);
     if constexpr (CP) {
       if (pend2) {
-        wgd_cp_store<F16>(pc, prow - 4 * GW, cpsoff, po[0]);
-        wgd_cp_store<F16>(pc, prow - 3 * GW, cpsoff, po[1]);
+        wgd_cp_store<F16, SC>(pc, prow - 4 * GW, cpsoff, po[0]);
+        wgd_cp_store<F16, SC>(pc, prow - 3 * GW, cpsoff, po[1]);
       }
       if (pending) {
-        wgd_cp_store<F16>(pc, prow - 2 * GW, cpsoff, pv[0]);
-        wgd_cp_store<F16>(pc, prow - GW, cpsoff, pv[1]);
+        wgd_cp_store<F16, SC>(pc, prow - 2 * GW, cpsoff, pv[0]);
+        wgd_cp_store<F16, SC>(pc, prow - GW, cpsoff, pv[1]);
       }
       for (; prow < pc.g.Bc * pc.g.Tc; prow += GW) {   // the rows the loop left
-        wgd_cp_load<CP == 2>(pc, prow, cploff, pv[0], srw);
-        wgd_cp_store<F16>(pc, prow, cpsoff, pv[0]);
+        wgd_cp_load<CP == 2, SC>(pc, prow, cploff, pv[0], srw);
+        wgd_cp_store<F16, SC>(pc, prow, cpsoff, pv[0]);
       }
     }
     t2 = WGD_CLK();
   } else if constexpr (CP != 0) {
     const StoreRowsW srw = CP == 2 ? dad_store_rows_w(pc, lane) : StoreRowsW{};
     for (int prow = gw; prow < pc.g.Bc * pc.g.Tc; prow += GW) {
-      f32x4 pv[3];
-      wgd_cp_load<CP == 2>(pc, prow, cploff, pv, srw);
-      wgd_cp_store<F16>(pc, prow, cpsoff, pv);
+      CpRaw pv[3];
+      wgd_cp_load<CP == 2, SC>(pc, prow, cploff, pv, srw);
+      wgd_cp_store<F16, SC>(pc, prow, cpsoff, pv);
     }
   }
   const int kh = lane >> 5;
@@ -901,8 +908,18 @@ __device__ __forceinline__ void wgrad_direct_body(const DadWgradArgs& a, const D
   const int s0 = split * per, s1 = min(total, s0 + per);
   wgd_lut(S.lut);   // (the tile's first barrier orders it before the first read)
   const int gw = __builtin_amdgcn_readfirstlane(tile * (WGD_THREADS / 64) + (int)(threadIdx.x >> 6));
-  wgd_tile<F16, CP>(a, ra, s0, s1, dblk * WGD_DB, a.wpart + (size_t)split * DAD_H * DAD_D, Xt, S.lut, gs, S.a.red, pc,
-                    gw, a.ntiles * (WGD_THREADS / 64));
+  float* const outf = a.wpart + (size_t)split * DAD_H * DAD_D;
+  const int GW = a.ntiles * (WGD_THREADS / 64);
+  // CP = 3: the `_s16` sibling of the store variant, clean rows read from an fp16 / bf16 store in their
+  // own type (block-uniform); a kernel of its own, so that the f32 kernels hold the f32 code alone
+  if constexpr (CP == 3) {
+    if (pc.xc_type() == DAD_STORE_F16)
+      wgd_tile<F16, 2, _Float16>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW);
+    else
+      wgd_tile<F16, 2, __bf16>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW);
+  } else {
+    wgd_tile<F16, CP>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW);
+  }
 }
 
 __global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct(DadWgradArgs a, DadReduceArgs ra) {
@@ -930,6 +947,16 @@ __global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_f16_cps(DadWg
                                                                           DadPrepArgs pc) {
   DAD_GUARD_BLOCK(WGD_THREADS);
   wgrad_direct_body<true, 2>(a, ra, pc);
+}
+__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_cps_s16(DadWgradArgs a, DadReduceArgs ra,
+                                                                          DadPrepArgs pc) {
+  DAD_GUARD_BLOCK(WGD_THREADS);
+  wgrad_direct_body<false, 3>(a, ra, pc);
+}
+__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_f16_cps_s16(DadWgradArgs a, DadReduceArgs ra,
+                                                                              DadPrepArgs pc) {
+  DAD_GUARD_BLOCK(WGD_THREADS);
+  wgrad_direct_body<true, 3>(a, ra, pc);
 }
 
 // ---------------------------------------------------------------- reduce + squared norms

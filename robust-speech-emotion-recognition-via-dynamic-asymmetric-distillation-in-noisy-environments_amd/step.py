@@ -19,22 +19,32 @@ import torch
 
 from . import _lib
 from .config import ConfigCache, ConfigView
-from .data import StoreFeats
+from .data import STORE_DTYPES, StoreFeats
 
 PRECISIONS = {"fp32": _lib.PREC_FP32, "bf16": _lib.PREC_BF16, "fp16": _lib.PREC_FP16}
 
 
-def _dev_batch(batch, device, labels=True):
+def _store_in_place(dtype, precision):
+    """A step of `precision` (_lib.PREC_*) reads the rows of a feature store of `dtype` where they lie:
+    an f32 store in every precision; an fp16 / bf16 store in the 16-bit precisions, whose row
+    preparation widens them on load (dad_batch.xc_dtype / xn_dtype).  The exact-f32 encoder and weight
+    gradient read f32 rows only."""
+    return dtype == torch.float32 or (dtype in STORE_DTYPES and precision != _lib.PREC_FP32)
+
+
+def _dev_batch(batch, device, labels=True, precision=_lib.PREC_FP32):
     """(x, pad, y, rows, lens): a padded batch, or a store-mode batch (data.StoreFeats: x is the
-    feature store and rows/lens locate each utterance in it, dad_batch.rowc..lenn)."""
+    feature store, of any dtype the step's precision reads in place (_store_in_place), and rows/lens
+    locate each utterance in it, dad_batch.rowc..lenn)."""
     ni = batch["net_input"]
     feats = ni["feats"]
     rows = lens = None
     if isinstance(feats, StoreFeats):
         sf = feats.store.feats
-        if sf.dtype == torch.float32 and sf.device == device:
+        # (torch dtypes are singletons: the f32 store's test stays an identity check, off the slow path)
+        if (sf.dtype is torch.float32 or _store_in_place(sf.dtype, precision)) and sf.device == device:
             x, rows, lens = sf, feats.rows, feats.lens
-        else:                      # the encoders read f32 rows: other stores are widened by dad_collate
+        else:                      # the FP32 step reads f32 rows: other stores are widened by dad_collate
             x = feats.materialize().to(device)
         pm = ni["padding_mask"]
         # (the loaders' own tensors need no conversion: skip the no-op .to()/.contiguous() dispatches)
@@ -61,14 +71,16 @@ def _dev_batch(batch, device, labels=True):
     return x, pad, y, None, None
 
 
-def _resident(batch, device, labels=True):
+def _resident(batch, device, labels=True, precision=_lib.PREC_FP32):
     """True when _dev_batch hands out the batch's own device tensors (no copy), i.e. the pointers a
-    step would prepare ahead are the ones the next step will see: f32 features (or an f32 store) on
-    `device`, a bool padding mask and int64 labels there, all contiguous."""
+    step would prepare ahead are the ones the next step will see: f32 features (or a store the step's
+    precision reads in place, _store_in_place) on `device`, a bool padding mask and int64 labels
+    there, all contiguous."""
     ni = batch["net_input"]
     feats, pm = ni["feats"], ni.get("padding_mask")
     if isinstance(feats, StoreFeats):
-        ok = feats.store.feats.dtype == torch.float32 and feats.store.feats.device == device
+        sf = feats.store.feats
+        ok = (sf.dtype is torch.float32 or _store_in_place(sf.dtype, precision)) and sf.device == device
     else:
         ok = (torch.is_tensor(feats) and feats.device == device and feats.dtype == torch.float32
               and feats.is_contiguous())
@@ -176,6 +188,7 @@ class DADStep:
         self._bufs = {}
         self._prepped_key = None       # identity of the batch the last step's tail launch prepared
         self.last_prepped = False
+        self._ahead = None             # the last step's (*prepped, *pending) out-parameters (last_ahead)
         self._next_keep = None
         self._shadow_dirty = False
         self.prep_under_exchange = 0 if prep_under_exchange is None else prep_under_exchange
@@ -184,6 +197,12 @@ class DADStep:
         self.refresh_shadow()
 
     # ----------------------------------------------------------------------------- state
+    @property
+    def last_ahead(self):
+        """(*prepped, *pending) as the library reported them for the next batch the last step() named
+        (dad_step_backward_ahead[_split]); (0, 0) when it named none or the batch did not qualify."""
+        return (0, 0) if self._ahead is None else (self._ahead[0].value, self._ahead[1].value)
+
     @property
     def ema_thresholds(self):
         return self.dacp[0:4]
@@ -296,6 +315,7 @@ class DADStep:
 
     _PREP_CFG = ("B", "T", "Bn", "Tn", "precision", "rng_mode", "seed", "counter", "warmup", "mask_len",
                  "start_hi", "weak_std", "strong_std", "feat_p")
+    # (xc_dtype / xn_dtype follow from xc / xn: a store tensor has one dtype)
     _PREP_BT = ("xc", "mc", "xn", "mn", "nw", "ns", "u", "start", "rowc", "lenc", "rown", "lenn")
 
     @classmethod
@@ -319,11 +339,11 @@ class DADStep:
         default like's + 1; only what the row preparation reads must be right, and the preparation
         ahead needs the same geometry), or None when its geometry differs (no preparation ahead)."""
         dev = self.device
-        xc, mc, yc, rc, lc = _dev_batch(clean_batch, dev)
+        xc, mc, yc, rc, lc = _dev_batch(clean_batch, dev, precision=self.precision)
         warm = epoch < self.view.WARMUP_EPOCHS
         rn = ln = None
         if noisy_batch is not None:
-            xn, mn, _, rn, ln = _dev_batch(noisy_batch, dev, labels=False)
+            xn, mn, _, rn, ln = _dev_batch(noisy_batch, dev, labels=False, precision=self.precision)
             Bn, Tn = mn.shape[0], mn.shape[1]
         elif warm:
             xn = mn = None
@@ -343,10 +363,14 @@ class DADStep:
         bt.xc, bt.mc, bt.yc = xc.data_ptr(), mc.data_ptr(), yc.data_ptr()
         if rc is not None:
             bt.rowc, bt.lenc = rc.data_ptr(), lc.data_ptr()
+            if xc.dtype is not torch.float32:       # (zero-initialised = DAD_STORE_F32)
+                bt.xc_dtype = STORE_DTYPES[xc.dtype]
         if xn is not None:
             bt.xn, bt.mn = xn.data_ptr(), mn.data_ptr()
             if rn is not None:
                 bt.rown, bt.lenn = rn.data_ptr(), ln.data_ptr()
+                if xn.dtype is not torch.float32:
+                    bt.xn_dtype = STORE_DTYPES[xn.dtype]
         keep = []
         if self.rng_mode == _lib.RNG_EXPLICIT:
             if draws is None:
@@ -370,7 +394,8 @@ class DADStep:
         ones the next step will use: device-resident tensors (a host batch would be copied here and
         copied again by the next step, whose rows would then not match; it prepares itself)."""
         clean, noisy = next_batch[0], next_batch[1]
-        if noisy is None or not (_resident(clean, self.device) and _resident(noisy, self.device, labels=False)):
+        if noisy is None or not (_resident(clean, self.device, precision=self.precision)
+                                 and _resident(noisy, self.device, labels=False, precision=self.precision)):
             return False
         if self.rng_mode == _lib.RNG_EXPLICIT:
             return _draws_resident(next_batch[2] if len(next_batch) > 2 else None, self.device)
@@ -386,7 +411,7 @@ class DADStep:
         lr).  FP16/BF16: its augmentation and 16-bit conversion then run inside this step's tail
         launch, on the CUs the tail leaves idle (dad_step_backward_ahead), and the next step()
         with that batch skips them.  Results are bit-identical with or without it.  Only
-        device-resident batches are prepared ahead (_ahead_ok: f32 features, bool masks, int64
+        device-resident batches are prepared ahead (_ahead_ok: f32 features or a store, bool masks, int64
         labels and, with explicit draws, the draws in DADStep's dtypes, all on the step's device);
         a host batch is ignored here and copied once, by the step that runs it.  The named
         batch's device tensors must keep their contents until that step.
@@ -419,8 +444,8 @@ class DADStep:
         else:
             ncfg = None
         pending = ctypes.c_int(0)
+        done = ctypes.c_int(0)
         if ncfg is not None:
-            done = ctypes.c_int(0)
             defer = self._defer_parts()
             if defer:
                 _lib.check(L.dad_step_backward_ahead_split(cfg, bt, st, _lib.ptr(ws), stream, ncfg, nbt, defer,
@@ -434,6 +459,7 @@ class DADStep:
                 self._next_keep = nkeep          # the preparation reads these until it has run
         else:
             _lib.check(L.dad_step_backward(cfg, bt, st, _lib.ptr(ws), stream), "dad_step_backward")
+        self._ahead = (done, pending)
         if pending.value:
             # the next batch's remaining rows on the side stream, from the end of the backward on:
             # under the all-reduce (and the optimizer), on CUs the exchange leaves idle
