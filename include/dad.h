@@ -71,11 +71,14 @@ extern "C" {
 #define DAD_T_KL_ON 32
 #define DAD_T_ECDA_ON 33
 #define DAD_T_RANGE 34        /* u32 bits, sticky (only the caller clears them; the buffer starts zero-filled):
-                                 DAD_RANGE_NONFINITE: a step's pooled embedding or logit was not finite (FP16: an
-                                 encoder operand beyond +-65504; any mode: non-finite features);
+                                 DAD_RANGE_NONFINITE: a step's pooled embedding or logit, or the step's gradient,
+                                 was not finite (FP16: an encoder operand beyond +-65504; any mode: non-finite
+                                 features; the gradient: its global norm, as dad_step_apply takes it, is NaN, inf
+                                 or beyond FLT_MAX -- that step's update was skipped);
                                  DAD_RANGE_POOL_TIMEOUT: a tail / class block gave up waiting for the tail
                                  launch's fused pooling (~0.2 s); that step's update was skipped (its total loss
-                                 is NaN).  dad_step_apply skips the update of any step whose total loss is not finite. */
+                                 is NaN).  dad_step_apply skips the update of any step whose total loss or
+                                 gradient norm is not finite. */
 #define DAD_RANGE_NONFINITE 1u
 #define DAD_RANGE_POOL_TIMEOUT 2u
 #define DAD_T_TAU_HAT 40      /* [4] batch quantile thresholds */

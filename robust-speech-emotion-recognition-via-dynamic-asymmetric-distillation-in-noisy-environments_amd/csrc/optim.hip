@@ -213,6 +213,17 @@ __global__ __launch_bounds__(DAD_OPTIM_THREADS) void dad_optim(DadOptimArgs a) {
   // reference would write NaN into all of them)
   const float total = a.grad[DAD_NPARAM + 12];
   if (!(fabsf(total) <= 3.402823466e38f)) return;
+  // so does a gradient whose global norm is not a finite float: a NaN or inf gradient element under a
+  // finite loss (norm = NaN would give coef = fminf(NaN, 1) = 1 and Adam would write NaN everywhere),
+  // and also a finite gradient whose norm overflows float.  Every wave holds the same norm, so the
+  // test is uniform; the step is flagged in the sticky range word (no other writer in this launch).
+  if (!(norm <= 3.402823466e38f)) {
+    if (blockIdx.x == 0 && tid == 0) {
+      uint32_t* range = reinterpret_cast<uint32_t*>(a.tailf + DAD_T_RANGE);
+      *range = *range | DAD_RANGE_NONFINITE;
+    }
+    return;
+  }
   if (blockIdx.x == 0) dacp_commit(cfg, a.grad, a.dacp, tid);
   const bool f16 = cfg.precision == DAD_PREC_FP16;
   if (vec)

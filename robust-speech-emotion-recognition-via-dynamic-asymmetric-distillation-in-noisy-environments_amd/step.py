@@ -538,10 +538,12 @@ class DADStep:
         """Device int32 scalar: the OR of the sticky range words (dad.h DAD_T_RANGE) of every batch
         shape this step has run (each (Bc, Bn) shape has its own tail buffer, so a ragged last batch
         does not hide a flag raised by the full-size batches).  Bits (`decode_range_flag`):
-        RANGE_NONFINITE (1): a pooled embedding or logit was not finite (FP16: an encoder operand
-        beyond +-65504; any mode: non-finite features); RANGE_POOL_TIMEOUT (2): the tail launch's
-        fused pooling hand-off timed out and that step's update was skipped.  (Any step whose total
-        loss is not finite leaves the parameters and state untouched.)  FP16/BF16: the encoder's
+        RANGE_NONFINITE (1): a pooled embedding or logit, or the step's gradient, was not finite (FP16:
+        an encoder operand beyond +-65504; any mode: non-finite features; the gradient: its global norm
+        is NaN, inf or beyond the float range, and that step's update was skipped); RANGE_POOL_TIMEOUT
+        (2): the tail launch's fused pooling hand-off timed out and that step's update was skipped.  (Any
+        step whose total loss or gradient norm is not finite leaves the parameters and state untouched.)
+        FP16/BF16: the encoder's
         ReLU works on the float bits (max(bits, 0)), so a NaN pre-activation with the sign bit set
         is dropped, not propagated as torch's ReLU would: NaN features can go unflagged there,
         while +-inf (an operand beyond the 16-bit range) is flagged.  `clear=True` resets every word after

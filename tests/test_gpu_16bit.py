@@ -127,7 +127,8 @@ def test_fp16_range_flag():
     gh.run_step(step, big, 60, with_draws=False)
     assert int(step.range_flag(clear=True)) != 0
     assert int(step.range_flag()) == 0                     # cleared
-    # (that step's loss was not finite, so its update poisoned the parameters: start over)
+    # (that step's loss was not finite, so dad_optim skipped its update and the parameters are the ones
+    # the first step left; start over from the seeded state all the same, so the last step is the first)
     gh.load_state(step, synth.make_state(21, 1))
     gh.run_step(step, inp, 60, with_draws=False)
     assert int(step.range_flag()) == 0

@@ -21,7 +21,7 @@ K = 7
 
 def _chain(cfg, precision, batches, st, ahead, wrong_at=None, split=False):
     step = gh.make_step(cfg, precision=precision, rng="counter", seed=5)
-    step.prep_under_exchange = split    # (the DP step's default: noisy rows on a side stream)
+    step.prep_under_exchange = split    # (off by default, in-launch; True: the clean rows on a side stream)
     gh.load_state(step, st)
     losses, prepped = [], []
     for k in range(K):

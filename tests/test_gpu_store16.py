@@ -38,9 +38,11 @@ def _features(rs, n):
     return (np.where(rs.rand(n, 768) < 0.5, -1.0, 1.0) * mag).astype(np.float32)
 
 
-def _layout(rs, groups):
+def _layout(rs, groups, filler=None):
     """Store layout of `groups` lists of utterance lengths: (features, sizes, offsets, index per group);
-    each utterance starts at an odd row, with 1 or 3 unrelated rows before it and some after the last."""
+    each utterance starts at an odd row, with 1 or 3 unrelated rows before it and some after the last.
+    filler(n) -> [n, 768]: what the unrelated rows hold instead of features (the utterances' rows and
+    the draws from `rs` are the same either way)."""
     sizes, offsets, index, row = [], [], [], 0
     for lens in groups:
         ids = []
@@ -52,7 +54,13 @@ def _layout(rs, groups):
             row += n
         index.append(ids)
     assert all(o % 2 == 1 for o in offsets)
-    return _features(rs, row + 3), np.array(sizes), np.array(offsets), index
+    feats = _features(rs, row + 3)
+    if filler is not None:
+        unrelated = np.ones(row + 3, bool)
+        for o, n in zip(offsets, sizes):
+            unrelated[o:o + n] = False
+        feats[unrelated] = filler(int(unrelated.sum()))
+    return feats, np.array(sizes), np.array(offsets), index
 
 
 _PROBLEMS = {}
