@@ -128,7 +128,19 @@ typedef struct dad_config {
   int32_t prepped;              /* FP16/BF16: 1 = the previous step's dad_step_backward_ahead prepared this
                                    batch's 16-bit rows (it reported *prepped = 1 for this cfg and batch), so
                                    the encoder skips the preparation; 0 = prepare them in this step */
-  int32_t reserved[4];
+  int32_t ragged;               /* FP16/BF16 store-mode steps: 1 = ragged mode, no launch of the step reads, computes or
+                                   writes anything for a 32-frame slab that lies wholly past its utterance's end
+                                   (slab c of utterance b is live iff c < ceil(len_b / 32), len_b = dad_batch.lenc /
+                                   lenn[b], read on the device; len_b = 0: no live slab).  Both batches must be store
+                                   batches (DAD_E_ARG otherwise; DAD_PREC_FP32: DAD_E_UNSUPPORTED), and mc / mn must
+                                   mark every frame t >= len_b as padding, as dad_collate_index writes them (frames
+                                   inside len_b may be marked too).  Buffer layouts, dense slab indices, RNG streams
+                                   and outputs are those of the dense step: the forward pass is bit-identical, the
+                                   gradient differs only by the order in which split partials are summed (not at all
+                                   when every slab is live).  A set prepared ragged is read by a ragged step only
+                                   (preparation ahead needs next_cfg->ragged == cfg->ragged).  0 = dense (the field
+                                   was reserved[0], always 0, before) */
+  int32_t reserved[3];
 } dad_config;
 
 /* One clean + one noisy collated batch (I/dataload_noisy.py:124-129 format). */
@@ -279,6 +291,33 @@ typedef struct dad_step_plan_info {
 } dad_step_plan_info;
 int dad_step_plan(const dad_config* cfg, const dad_config* next_cfg, const dad_batch* next_batch, int defer,
                   int cus, dad_step_plan_info* out);
+/* Host-only: how a ragged step (cfg->ragged = 1, see dad_config) on a device of `cus` compute units divides
+ * its live slabs, computed from HOST copies of the two length arrays (lenc [B], lenn [Bn]; lenn may be NULL
+ * in a warm-up step) by the functions the kernels call on the device lengths.  Live lists: teachers run the
+ * live weak slabs, students the live clean slabs and then the live strong slabs, both in (utterance, slab)
+ * order; the weight gradient runs the student list.
+ *   enc[3 wg ..]   (teacher 1/0, first live job, count) of encoder workgroup wg < enc_grid (= ws_nt + ws_ns of
+ *                  dad_step_plan: the grid does not depend on the lengths); live job k of a teacher is entry k
+ *                  of the live weak list, of a student entry k of the student list
+ *   split[2 s ..]  [first, end) of weight-gradient split s < splits in the student list
+ * enc_capacity / split_capacity (in): the triples / pairs the caller's arrays hold.  enc_grid and splits are
+ * written first; DAD_E_ARG (nothing else written) when a capacity is too small.  The encoder's shares are even
+ * by live 16-row sub-slabs, as the dense step's, unless one would exceed the kernel's 256-job table (many
+ * utterances of at most 16 frames sorted together): that role's jobs are then split evenly by count.  So
+ * max_enc_range never exceeds 256, and max_split_utts never 64, the weight gradient's per-split table.  No
+ * device call.
+ * Diagnostics and tests. */
+typedef struct dad_ragged_plan {
+  int32_t live_clean, live_noisy;       /* live slabs per branch (weak = strong = live_noisy) */
+  int32_t enc_grid, splits;
+  int32_t max_enc_range;                /* the most live jobs any encoder workgroup runs */
+  int32_t max_split_utts;               /* the most utterances any weight-gradient split touches */
+  int32_t enc_capacity, split_capacity; /* in */
+  int32_t* enc;                         /* in: [3 * enc_capacity] */
+  int32_t* split;                       /* in: [2 * split_capacity] */
+} dad_ragged_plan;
+int dad_step_ragged_plan(const dad_config* cfg, const int32_t* lenc, const int32_t* lenn, int cus,
+                         dad_ragged_plan* out);
 int dad_step_apply(const dad_config* cfg, const dad_state* st, void* workspace, void* stream);
 int dad_step(const dad_config* cfg, const dad_batch* batch, const dad_state* st,
              void* workspace, void* stream);

@@ -60,7 +60,8 @@ class DadConfig(ctypes.Structure):
         ("one_m_beta2", ctypes.c_float), ("adam_eps", ctypes.c_float), ("weight_decay", ctypes.c_float),
         ("ema_m", ctypes.c_float), ("ema_one_m", ctypes.c_float),
         ("dacp_beta", ctypes.c_float), ("dacp_one_m_beta", ctypes.c_float),
-        ("splits", ctypes.c_int32), ("prepped", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4),
+        ("splits", ctypes.c_int32), ("prepped", ctypes.c_int32), ("ragged", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 3),
     ]
 
 
@@ -83,6 +84,14 @@ class DadStepPlanInfo(ctypes.Structure):
                   "tail_prep", "tail_prep_clean_only", "wgrad_grid", "wgrad_clean", "wgrad_store", "reduce_grid",
                   "prepped", "pending")]
                 + [(n, ctypes.c_char_p) for n in ("encode", "tail", "wgrad", "reduce")])
+
+
+class DadRaggedPlan(ctypes.Structure):
+    """dad.h dad_ragged_plan (dad_step_ragged_plan); `ragged_plan()` below fills and unpacks it."""
+    _fields_ = ([(n, ctypes.c_int32) for n in
+                 ("live_clean", "live_noisy", "enc_grid", "splits", "max_enc_range", "max_split_utts",
+                  "enc_capacity", "split_capacity")]
+                + [("enc", ctypes.POINTER(ctypes.c_int32)), ("split", ctypes.POINTER(ctypes.c_int32))])
 
 
 class DadEvalArgs(ctypes.Structure):
@@ -121,6 +130,9 @@ EXPORTS = {
                                              ctypes.c_void_p, ctypes.c_int]),
     "dad_step_plan": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.POINTER(DadConfig), ctypes.POINTER(DadBatch),
                                      ctypes.c_int, ctypes.c_int, ctypes.POINTER(DadStepPlanInfo)]),
+    "dad_step_ragged_plan": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.POINTER(ctypes.c_int32),
+                                            ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                            ctypes.POINTER(DadRaggedPlan)]),
     "dad_step_apply": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.POINTER(DadState),
                                       ctypes.c_void_p, ctypes.c_void_p]),
     "dad_step": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.POINTER(DadBatch), ctypes.POINTER(DadState),
@@ -181,6 +193,10 @@ EXPORTS = {
     "dad_comm_destroy": (ctypes.c_int, [ctypes.c_void_p]),
 }
 
+# Entry points added without an ABI bump: a library of the same ABI version built before them loads, and
+# the feature that needs one reports the stale build when it is asked for (require()).
+OPTIONAL_EXPORTS = ("dad_step_ragged_plan",)
+
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]
 
@@ -204,6 +220,8 @@ def lib():
     if not hasattr(L, "dad_abi_version"):
         raise DadError("%s predates ABI 6 (no dad_abi_version): rebuild it (__graft_entry__.build())" % path)
     for name, (res, args) in EXPORTS.items():
+        if name in OPTIONAL_EXPORTS and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -213,6 +231,36 @@ def lib():
                        % (path, ver, DAD_ABI_VERSION))
     _LIB = L
     return L
+
+
+def require(name, what):
+    """The optional entry point `name` (OPTIONAL_EXPORTS), or DadError: the library predates `what`."""
+    L = lib()
+    if not hasattr(L, name):
+        raise DadError("%s has no %s, which %s needs: rebuild it (__graft_entry__.build())"
+                       % (_build.lib_path(os.environ.get("DAD_LIB_VARIANT") or None), name, what))
+    return getattr(L, name)
+
+
+def ragged_plan(cfg, lenc, lenn, cus):
+    """dad_step_ragged_plan for host length lists: {'live_clean', 'live_noisy', 'max_enc_range',
+    'max_split_utts', 'enc': [(teacher, first live job, count)], 'split': [(first, end)]}."""
+    fn = require("dad_step_ragged_plan", "the ragged plan")
+    out = DadRaggedPlan()
+    lc = (ctypes.c_int32 * max(len(lenc), 1))(*[int(v) for v in lenc])
+    ln = None if lenn is None else (ctypes.c_int32 * max(len(lenn), 1))(*[int(v) for v in lenn])
+    rc = fn(cfg, lc, ln, int(cus), out)      # sizes first: no arrays yet (DAD_E_ARG)
+    if rc != E_ARG or out.enc_grid <= 0:
+        check(rc if rc else E_ARG, "dad_step_ragged_plan")
+    enc = (ctypes.c_int32 * (3 * out.enc_grid))()
+    split = (ctypes.c_int32 * (2 * max(out.splits, 1)))()
+    out.enc, out.split = enc, split
+    out.enc_capacity, out.split_capacity = out.enc_grid, max(out.splits, 1)
+    check(fn(cfg, lc, ln, int(cus), out), "dad_step_ragged_plan")
+    return {"live_clean": out.live_clean, "live_noisy": out.live_noisy, "max_enc_range": out.max_enc_range,
+            "max_split_utts": out.max_split_utts,
+            "enc": [tuple(enc[3 * i:3 * i + 3]) for i in range(out.enc_grid)],
+            "split": [tuple(split[2 * i:2 * i + 2]) for i in range(out.splits)]}
 
 
 def check(rc, what=""):

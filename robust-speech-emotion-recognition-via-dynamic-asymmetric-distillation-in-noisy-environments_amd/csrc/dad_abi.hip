@@ -18,12 +18,16 @@ int device_cus(int* out) {
   return DAD_OK;
 }
 
-int launch_prep(const DadPrepArgs& p, hipStream_t stream) {
+// the standalone preparation's kernel: the ragged sibling, the 16-bit-store sibling, or dad_prep
+static void (*prep_kernel_of(const DadPrepArgs& p, bool ragged))(DadPrepArgs) {
+  return ragged ? dad_prep_rg : dad_prep_s16_needed(p) ? dad_prep_s16 : dad_prep;
+}
+
+int launch_prep(const DadPrepArgs& p, hipStream_t stream, bool ragged) {
   int cus = 0;
   const int rc = device_cus(&cus);
   if (rc) return rc;
-  hipLaunchKernelGGL(dad_prep_s16_needed(p) ? dad_prep_s16 : dad_prep, dim3(prep_grid_of(cus)), dim3(DAD_PREP_THREADS), 0,
-                     stream, p);
+  hipLaunchKernelGGL(prep_kernel_of(p, ragged), dim3(prep_grid_of(cus)), dim3(DAD_PREP_THREADS), 0, stream, p);
   DAD_TRY(hipGetLastError());
   return DAD_OK;
 }
@@ -64,6 +68,8 @@ int check_step_args(const dad_config* cfg, const dad_batch* bt, const dad_state*
   if (explicit_rng && cfg->p_drop > 0.0f && (!bt->keep1 || (!cfg->warmup && !bt->keep2))) return DAD_E_ARG;
   if (explicit_rng && !cfg->warmup && !has_explicit_draws(bt)) return DAD_E_ARG;
   if (!rows_paired(bt)) return DAD_E_ARG;
+  const int rrc = check_ragged_batch(cfg, bt);
+  if (rrc) return rrc;
   return check_batch_dtypes(cfg, bt);
 }
 
@@ -96,6 +102,11 @@ const WgradLaunch kWgradLaunch[] = {   // [plan.wgrad - K_WGRAD_F32]
     {nullptr, dad_wgrad_direct_cps, WGD_THREADS},
     {dad_wgrad_direct_f16, nullptr, WGD_THREADS}, {nullptr, dad_wgrad_direct_f16_cp, WGD_THREADS},
     {nullptr, dad_wgrad_direct_f16_cps, WGD_THREADS}};
+// the ragged step's siblings (dad_kernels.h `_rg`) of the 16-bit kernels above
+const EncodeLaunch kEncodeLaunchRg[] = {   // [plan.encode - K_ENCODE_WP]
+    {dad_encode_wp_rg, DAD_ENC_WS_THREADS}, {dad_encode_wp_f16_rg, DAD_ENC_WS_THREADS}};
+const WgradLaunch kWgradLaunchRg[2] = {    // [fp16]: plain, and with the (ragged, store) next batch's clean rows
+    {dad_wgrad_direct_rg, dad_wgrad_direct_cps_rg, WGD_THREADS}, {dad_wgrad_direct_f16_rg, dad_wgrad_direct_f16_cps_rg, WGD_THREADS}};
 struct ReduceLaunch { void (*kernel)(DadReduceArgs); int threads; };
 const ReduceLaunch kReduceLaunch[] = {{dad_reduce, DAD_REDUCE_THREADS}, {dad_reduce_w, 64}};   // [plan.reduce - K_REDUCE]
 
@@ -165,6 +176,14 @@ int dad_step_plan(const dad_config* cfg, const dad_config* next_cfg, const dad_b
                             p.wgrad_store, p.reduce_grid, p.prepped, p.pending, kStepKernelName[p.encode],
                             kStepKernelName[p.tail], kStepKernelName[p.wgrad], kStepKernelName[p.reduce]};
   return DAD_OK;
+}
+
+int dad_step_ragged_plan(const dad_config* cfg, const int32_t* lenc, const int32_t* lenn, int cus, dad_ragged_plan* out) {
+  const int rc = check_cfg(cfg);
+  if (rc) return rc;
+  if (!dad_prec16(cfg->precision)) return DAD_E_UNSUPPORTED;
+  if (cus < 2 || !out || !lenc || (!cfg->warmup && !lenn)) return DAD_E_ARG;
+  return ragged_plan(cfg, lenc, lenn, cus, out);
 }
 
 int dad_workspace_bytes(const dad_config* cfg, size_t* bytes) {
@@ -242,11 +261,11 @@ static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const
     tk_mark(TK_E0, stream);
     if (plan.prep_grid) {
       const DadPrepArgs own = prep_args(cfg, bt, xs16);
-      hipLaunchKernelGGL(dad_prep_s16_needed(own) ? dad_prep_s16 : dad_prep, dim3(plan.prep_grid), dim3(DAD_PREP_THREADS),
-                         0, stream, own);
+      hipLaunchKernelGGL(prep_kernel_of(own, cfg->ragged != 0), dim3(plan.prep_grid), dim3(DAD_PREP_THREADS), 0, stream,
+                         own);
       DAD_TRY(hipGetLastError());
     }
-    const EncodeLaunch& enc = kEncodeLaunch[plan.encode - K_ENCODE_F32];
+    const EncodeLaunch& enc = cfg->ragged ? kEncodeLaunchRg[plan.encode - K_ENCODE_WP] : kEncodeLaunch[plan.encode - K_ENCODE_F32];
     hipLaunchKernelGGL(enc.kernel, dim3(plan.encode_grid), dim3(enc.threads), 0, stream, ea);
     DAD_TRY(hipGetLastError());
     tk_mark(TK_E1, stream);
@@ -269,8 +288,9 @@ static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const
   pa.part_cnt = part_cnt; pa.cnt_tot = cnt_tot;
   pa.eflag = eflag; pa.tail_terms = st->tail + DAD_T_ECDA_TERM;
   pa.range_flag = reinterpret_cast<uint32_t*>(st->tail + DAD_T_RANGE);
+  if (cfg->ragged) { pa.lenc = bt->lenc; pa.lenn = bt->lenn; }
   if (plan.pool_grid) {
-    hipLaunchKernelGGL(dad_pool, dim3(plan.pool_grid), dim3(DAD_POOL_THREADS), 0, stream, pa);
+    hipLaunchKernelGGL(cfg->ragged ? dad_pool_rg : dad_pool, dim3(plan.pool_grid), dim3(DAD_POOL_THREADS), 0, stream, pa);
     DAD_TRY(hipGetLastError());
     tk_mark(TK_POOL, stream);
   } else {
@@ -307,8 +327,10 @@ static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const
     case K_TAIL: hipLaunchKernelGGL(dad_tail, tgrid, tblock, 0, stream, ta); break;
     case K_TAIL_ECDA: hipLaunchKernelGGL(dad_tail_ecda, tgrid, tblock, 0, stream, ta, ca); break;
     default:   // (the `_s16` sibling when the rows it prepares lie in a 16-bit store, dad_kernels.h)
-      hipLaunchKernelGGL(pp.x16 && dad_prep_s16_needed(pp) ? dad_tail_ecda_w_s16 : dad_tail_ecda_w, tgrid, tblock, 0,
-                         stream, ta, ca, pp, pa);
+      //  a ragged step: its `_rg` sibling, whose pooling sums live slabs only)
+      hipLaunchKernelGGL(cfg->ragged ? dad_tail_ecda_w_rg
+                                     : pp.x16 && dad_prep_s16_needed(pp) ? dad_tail_ecda_w_s16 : dad_tail_ecda_w,
+                         tgrid, tblock, 0, stream, ta, ca, pp, pa);
       break;
   }
   DAD_TRY(hipGetLastError());
@@ -341,7 +363,11 @@ static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const
   ra.pool_abort = plan.pool_grid ? nullptr : pool_ready + DAD_POOL_ABORT;
   ra.splits = plan.splits; ra.wpart = wa.wpart;
   const WgradLaunch& wg = kWgradLaunch[plan.wgrad - K_WGRAD_F32];
-  if (wg.cp) {
+  if (cfg->ragged) {
+    const WgradLaunch& rg = kWgradLaunchRg[cfg->precision == DAD_PREC_FP16];
+    if (plan.wgrad_clean) hipLaunchKernelGGL(rg.cp, dim3(plan.wgrad_grid), dim3(rg.threads), 0, stream, wa, ra, pcw);
+    else hipLaunchKernelGGL(rg.kernel, dim3(plan.wgrad_grid), dim3(rg.threads), 0, stream, wa, ra);
+  } else if (wg.cp) {
     auto cp = wg.cp;
     if (plan.wgrad_store && pcw.xc_type() != DAD_STORE_F32)
       cp = cfg->precision == DAD_PREC_FP16 ? dad_wgrad_direct_f16_cps_s16 : dad_wgrad_direct_cps_s16;
@@ -399,13 +425,14 @@ int dad_step_prepare_rows(const dad_config* cfg, const dad_batch* bt, void* work
   if ((parts & DAD_PREP_NOISY) && (!bt->xn || (cfg->rng_mode == DAD_RNG_EXPLICIT && !has_explicit_draws(bt))))
     return DAD_E_ARG;
   if (!rows_paired(bt)) return DAD_E_ARG;
+  if (cfg->ragged && (((parts & DAD_PREP_CLEAN) && !bt->lenc) || ((parts & DAD_PREP_NOISY) && !bt->lenn))) return DAD_E_ARG;
   const int drc = check_batch_dtypes(cfg, bt);
   if (drc) return drc;
   if (parts == 0) return DAD_OK;
   const DadWs L = dad_ws_layout(geom_of(cfg), max_splits_of(cfg), cfg->precision);
   DadPrepArgs p = prep_args(cfg, bt, ws_ptr<uint16_t>(workspace, L.xs16 + (cfg->counter & 1u) * L.x16set));
   prep_only(p, parts);
-  return launch_prep(p, (hipStream_t)stream);
+  return launch_prep(p, (hipStream_t)stream, cfg->ragged != 0);
 }
 
 int dad_step_apply(const dad_config* cfg, const dad_state* st, void* workspace, void* stream_) {

@@ -315,6 +315,174 @@ static inline __host__ __device__ void dad_wp_job_range(int wg, int nt, int ns, 
   j1 = j[1];
 }
 
+// ---------------------------------------------------------------------------------
+// Ragged mode (dad_config.ragged): the live lists, shared by the kernels and the host plan
+// (dad_step_ragged_plan).  Slab c of an utterance of len frames (nc slabs in the padded batch) is
+// LIVE iff c < ceil(len / 32); a ragged step touches live slabs only.  The utterances of a step
+// form one list, clean [0, Bc) then noisy [Bc, Bc + Bn) (Bn = 0 in a warm-up step), with three
+// exclusive prefixes over it ([n + 1] ints each, entry n = the total):
+//   ps   live slabs               pss  live 16-row sub-slabs (what an encoder job costs)
+//   pz   utterances with at least one live slab (the weight gradient's per-split utterance slots)
+// Live index k of the student list (clean then strong) is slab k - ps[u] of utterance u =
+// dad_live_find(ps, n, k); the weak list is the noisy part of the same prefix.  Buffers keep
+// their dense slab numbering: the maps below return dense (utterance, slab) pairs.
+static inline __host__ __device__ int dad_live_slabs(int len, int nc) {
+  if (len <= 0) return 0;
+  if (len >= nc * DAD_SLAB) return nc;
+  return (len + DAD_SLAB - 1) / DAD_SLAB;
+}
+static inline __host__ __device__ int dad_live_subs(int len, int T) {
+  const int l = len < T ? len : T;
+  return l > 0 ? (l + 15) / 16 : 0;
+}
+// largest u in [u0, u1) with pre[u] - pre[u0] <= k  (u1 > u0; pre nondecreasing)
+template <typename K>
+static inline __host__ __device__ int dad_live_find_in(const int* pre, int u0, int u1, K k) {
+  int lo = u0, hi = u1 - 1;
+  const int base = pre[u0];
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((K)(pre[mid] - base) <= k) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+static inline __host__ __device__ int dad_live_find(const int* pre, int n, int k) {
+  return dad_live_find_in<int>(pre, 0, n, k);
+}
+// dad_live_jobs_at over utterances [u0, u1) of the list: the live-job boundary (relative to ps[u0])
+// nearest to x cumulative live sub-slabs of that part.  With every slab live it is
+// dad_live_jobs_at(x, nc, L, J) of the dense encoder.
+static inline __host__ __device__ int dad_rg_jobs_at(const int* ps, const int* pss, int u0, int u1, float x) {
+  if (x <= 0.0f || u1 <= u0) return 0;
+  const int u = dad_live_find_in<float>(pss, u0, u1, x);
+  const float r = x - (float)(pss[u] - pss[u0]);
+  const int c0 = (int)(0.5f * r + 0.5f);
+  const int nl = ps[u + 1] - ps[u];
+  return ps[u] - ps[u0] + (c0 < nl ? c0 : nl);
+}
+// dad_wp_job_range on the live lists: workgroup wg's [j0, j1) of live jobs (teachers: the live weak
+// list; students: the student list), the same even split by live sub-slabs over the same nt + ns
+// grid.  n = Bc + Bn (Bn = 0 in a warm-up step).  by_slabs: the role's jobs split evenly by count
+// instead (dad_rg_by_slabs): ranges of at most ceil(live / parts) <= ceil(dense jobs / parts) jobs, which
+// the grid wp_split chose keeps within the kernel's 256-job table.
+static inline __host__ __device__ void dad_rg_job_range(int wg, int nt, int ns, const int* ps, const int* pss, int Bc,
+                                                        int n, bool by_slabs, bool& teacher, int& j0, int& j1) {
+  teacher = wg < nt;
+  const int k = teacher ? wg : wg - nt, parts = teacher ? nt : ns;
+  const float tc = (float)pss[Bc], tn = (float)(pss[n] - pss[Bc]);
+  const float tot = teacher ? tn : tc + tn;
+  const int Lc = ps[Bc], Ln = ps[n] - ps[Bc];
+  int j[2];
+  for (int e = 0; e < 2; ++e) {
+    const int kk = k + e;
+    if (kk >= parts) { j[e] = teacher ? Ln : Lc + Ln; continue; }
+    if (by_slabs) { j[e] = (int)((long long)(teacher ? Ln : Lc + Ln) * kk / parts); continue; }
+    const float x = tot * (float)kk / (float)parts;
+    if (teacher) j[e] = dad_rg_jobs_at(ps, pss, Bc, n, x);
+    else j[e] = x <= tc ? dad_rg_jobs_at(ps, pss, 0, Bc, x) : Lc + dad_rg_jobs_at(ps, pss, Bc, n, x - tc);
+  }
+  j0 = j[0];
+  j1 = j[1];
+}
+// A range of the split by sub-slabs holds at most its sub-slabs (a job has at least one) plus the two
+// boundaries' rounding: a role with at most 250 live sub-slabs per workgroup fits the 256-job table
+// whatever the lengths.
+static inline __host__ __device__ bool dad_rg_subs_fit(int nt, int ns, const int* pss, int Bc, int n, bool teacher) {
+  const long long tot = teacher ? pss[n] - pss[Bc] : pss[n];
+  return tot <= 250ll * (teacher ? nt : ns);
+}
+// The split rule of a role (host form; the kernel evaluates the ranges in parallel): by count when a range
+// of the split by sub-slabs would exceed `maxj` jobs.
+static inline bool dad_rg_by_slabs(int nt, int ns, const int* ps, const int* pss, int Bc, int n, bool teacher, int maxj) {
+  if (dad_rg_subs_fit(nt, ns, pss, Bc, n, teacher)) return false;
+  for (int wg = teacher ? 0 : nt; wg < (teacher ? nt : nt + ns); ++wg) {
+    bool t;
+    int j0, j1;
+    dad_rg_job_range(wg, nt, ns, ps, pss, Bc, n, false, t, j0, j1);
+    if (j1 - j0 > maxj) return true;
+  }
+  return false;
+}
+// live index k of the student list (teacher: of the weak list) -> list utterance u and slab c
+static inline __host__ __device__ void dad_rg_slab(const int* ps, int Bc, int n, bool teacher, int k, int& u, int& c) {
+  const int kk = teacher ? k + ps[Bc] : k;
+  u = dad_live_find(ps, n, kk);
+  c = kk - ps[u];
+}
+// ... -> the dense job number of dad_wp_job_range (teacher: weak slab; student: clean slab, or Jc + strong slab)
+static inline __host__ __device__ int dad_rg_dense_job(const int* ps, int Bc, int n, int ncc, int ncn, bool teacher,
+                                                       int k) {
+  int u, c;
+  dad_rg_slab(ps, Bc, n, teacher, k, u, c);
+  if (u < Bc) return u * ncc + c;
+  return (teacher ? 0 : Bc * ncc) + (u - Bc) * ncn + c;
+}
+// wg_range's formula (wgrad.hip) on a list of `total` slabs: split's contiguous share [s0, s1)
+static inline __host__ __device__ void dad_wg_share(int total, int splits, int split, int& s0, int& s1) {
+  const int per = (total + splits - 1) / splits;
+  s0 = split * per;
+  const int e = s0 + per;
+  s1 = e < total ? e : total;
+  if (s0 > s1) s0 = s1;
+}
+// host: the three prefixes from host copies of the lengths (the kernels: dad_live_prefix_lds)
+static inline void dad_live_prefix_host(const int32_t* lenc, int Bc, int ncc, int Tc, const int32_t* lenn, int Bn, int ncn,
+                                        int Tn, int* ps, int* pss, int* pz) {
+  int a = 0, b = 0, z = 0;
+  for (int u = 0; u < Bc + Bn; ++u) {
+    const bool noisy = u >= Bc;
+    const int len = noisy ? lenn[u - Bc] : lenc[u];
+    const int l = dad_live_slabs(len, noisy ? ncn : ncc);
+    ps[u] = a; pss[u] = b; pz[u] = z;
+    a += l;
+    b += l ? dad_live_subs(len, noisy ? Tn : Tc) : 0;
+    z += l ? 1 : 0;
+  }
+  ps[Bc + Bn] = a; pss[Bc + Bn] = b; pz[Bc + Bn] = z;
+}
+#ifdef __HIPCC__
+// device: the same prefixes in LDS (n + 1 ints each, n = Bc + Bn <= 2 * DAD_MAX_BATCH), built by the
+// whole workgroup from the device lengths: every thread fills entries, wave 0 scans them (lane l a
+// run of ceil(n / 64) entries, the 64 run sums by a wave scan; B, Bn <= 64: two entries per lane).
+// Ends with a barrier; the caller's LDS behind the three arrays must be free until then.
+__device__ __forceinline__ void dad_live_prefix_lds(const int32_t* lenc, int Bc, int ncc, int Tc, const int32_t* lenn,
+                                                    int Bn, int ncn, int Tn, int* ps, int* pss, int* pz) {
+  const int n = Bc + Bn;
+  for (int u = threadIdx.x; u < n; u += blockDim.x) {
+    const bool noisy = u >= Bc;
+    const int len = noisy ? lenn[u - Bc] : lenc[u];
+    const int l = dad_live_slabs(len, noisy ? ncn : ncc);
+    ps[u] = l;
+    pss[u] = l ? dad_live_subs(len, noisy ? Tn : Tc) : 0;
+    pz[u] = l ? 1 : 0;
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    const int per = (n + 63) / 64;
+    const int i0 = min(lane * per, n), i1 = min(i0 + per, n);
+    int s[3] = {0, 0, 0};
+    for (int i = i0; i < i1; ++i) { s[0] += ps[i]; s[1] += pss[i]; s[2] += pz[i]; }
+    int inc[3] = {s[0], s[1], s[2]};
+    for (int o = 1; o < 64; o <<= 1)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const int t = __shfl_up(inc[q], o, 64);
+        if (lane >= o) inc[q] += t;
+      }
+    int e[3] = {inc[0] - s[0], inc[1] - s[1], inc[2] - s[2]};
+    for (int i = i0; i < i1; ++i) {
+      const int a = ps[i], b = pss[i], z = pz[i];
+      ps[i] = e[0]; pss[i] = e[1]; pz[i] = e[2];
+      e[0] += a; e[1] += b; e[2] += z;
+    }
+    if (lane == 63) { ps[n] = inc[0]; pss[n] = inc[1]; pz[n] = inc[2]; }
+  }
+  __syncthreads();
+}
+#endif
+
 // Workspace layout (bytes), shared by host and device.  All offsets 256-B aligned.
 //   slab-indexed buffers: clean slabs [0, Bc*ncc), noisy slabs after them.
 struct DadWs {

@@ -31,4 +31,5 @@ inline Keys keys_of(const dad_config* c) {
 // compute units of the current device (cached per device)
 int device_cus(int* out);
 // standalone preparation of one set (dad_prep, prep_grid_of the current device)
-int launch_prep(const DadPrepArgs& p, hipStream_t stream);
+// (ragged: dad_prep_rg, the preparation of a ragged step's set)
+int launch_prep(const DadPrepArgs& p, hipStream_t stream, bool ragged = false);

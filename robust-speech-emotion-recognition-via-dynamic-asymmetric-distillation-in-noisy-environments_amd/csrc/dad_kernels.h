@@ -61,6 +61,7 @@ struct DadPoolArgs {
   uint32_t* ready;        // pooling fused into dad_tail_ecda_w: pool items done, DAD_POOL_SHARDS
                           // counters 128 B apart (zeroed by the step's encoder); NULL: the
                           // separate dad_pool launch
+  const int32_t* lenc; const int32_t* lenn;   // ragged kernels: dad_batch.lenc / lenn (only live slabs hold partials)
 };
 
 struct DadEncodeArgs {
@@ -220,6 +221,20 @@ __global__ void dad_wgrad_direct_cps(DadWgradArgs a, DadReduceArgs r, DadPrepArg
 __global__ void dad_wgrad_direct_f16_cps(DadWgradArgs a, DadReduceArgs r, DadPrepArgs pc);
 __global__ void dad_wgrad_direct_cps_s16(DadWgradArgs a, DadReduceArgs r, DadPrepArgs pc);
 __global__ void dad_wgrad_direct_f16_cps_s16(DadWgradArgs a, DadReduceArgs r, DadPrepArgs pc);
+// The `_rg` siblings: the kernels of a ragged step (dad_config.ragged: FP16 / BF16, both batches store
+// batches), launched in place of the kernels the step plan names, with the same grids.  They read the
+// batch's lengths on the device and touch live slabs only (dad_common.h, "Ragged mode"); kernels and units
+// of their own, so that the dense kernels compile to what they did without the mode.  The row loads take
+// the store's type at run time (f32, fp16 or bf16: one sibling stands for the f32 kernel and its `_s16` form).
+__global__ void dad_prep_rg(DadPrepArgs a);
+__global__ void dad_encode_wp_rg(DadEncodeArgs a);
+__global__ void dad_encode_wp_f16_rg(DadEncodeArgs a);
+__global__ void dad_pool_rg(DadPoolArgs a);
+__global__ void dad_tail_ecda_w_rg(DadTailArgs ta, DadEcdaArgs ca, DadPrepArgs pa, DadPoolArgs pl);
+__global__ void dad_wgrad_direct_rg(DadWgradArgs a, DadReduceArgs r);
+__global__ void dad_wgrad_direct_f16_rg(DadWgradArgs a, DadReduceArgs r);
+__global__ void dad_wgrad_direct_cps_rg(DadWgradArgs a, DadReduceArgs r, DadPrepArgs pc);       // (next batch: ragged too)
+__global__ void dad_wgrad_direct_f16_cps_rg(DadWgradArgs a, DadReduceArgs r, DadPrepArgs pc);
 __global__ void dad_reduce(DadReduceArgs a);
 __global__ void dad_reduce_w(DadReduceArgs a);
 __global__ void dad_norm(float* grad, float* normpart, float inv_world);

@@ -101,7 +101,11 @@ __device__ __forceinline__ int dad_prep_tstart(const DadPrepArgs& a, int b) {
 // 40.2 us against 29.8 for a padded batch (events, one box).
 // S: the source element type of every row this call prepares; clean / noisy: the parts of the set it
 // prepares (dad_prep_dispatch: a.clean and every noisy row, unless the two parts differ in type).
-template <int NOISE, bool F16, int R, bool STOREN, typename S = float>
+// RG (the ragged step's kernels, store batches): row t of utterance b is skipped -- no load, no draw, no
+// store -- when it lies in a dead slab, t >= 32 ceil(len_b / 32); rows past len_b inside the last live slab
+// are prepared as ever.  The predicate is wave-uniform (one row per wave); the grid-stride loop is kept
+// (the pass is HBM-bound: the waves that skip more rows finish sooner and leave the bandwidth to the rest).
+template <int NOISE, bool F16, int R, bool STOREN, typename S = float, bool RG = false>
 __device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, int nwaves, int lane, int clean,
                                               bool noisy_part) {
   const DadGeom& G = a.g;
@@ -128,6 +132,7 @@ __device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, in
     for (int e = 0; e < 4; ++e) kp[k][e] = dad_feat_keep(a.u, a.key_feat, 256 * k + 4 * lane + e, a.feat_p);
   for (int base = (clean ? 0 : Nc) + wave; base < N; base += R * nwaves) {
     typename DadSrc<S>::raw v[R][3];
+    bool live[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int u = min(base + r * nwaves, N - 1);
@@ -135,6 +140,12 @@ __device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, in
       const int un = noisy ? u - Nc : u;
       const int T = noisy ? G.Tn : G.Tc;
       const int b = un / T, t = un - b * T;
+      live[r] = true;
+      if constexpr (RG) {
+        const int len = (STOREN && noisy) ? __builtin_amdgcn_readlane(sn_len, b) : (noisy ? a.src.lenn : a.src.lenc)[b];
+        live[r] = t < DAD_SLAB * dad_live_slabs(len, noisy ? G.ncn : G.ncc);
+        if (!live[r]) continue;
+      }
       size_t srow;
       if (STOREN && noisy) {   // (b is wave-uniform: the wave's row is)
         const uint64_t base = (uint64_t)__builtin_amdgcn_readlane(sn_lo, b) |
@@ -151,6 +162,7 @@ __device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, in
     for (int r = 0; r < R; ++r) {
       const int u = base + r * nwaves;
       if (u >= N) break;
+      if (RG && !live[r]) continue;
       if (u < Nc) {
         char* o = reinterpret_cast<char*>(oc + (size_t)u * DAD_D + 4 * lane);
 #pragma unroll
@@ -199,38 +211,39 @@ __device__ __forceinline__ void dad_prep_rows(const DadPrepArgs& a, int wave, in
 }
 
 // runtime dispatch on the set's precision and draw source (wave-uniform)
-template <int R, bool STOREN, typename S>
+template <int R, bool STOREN, typename S, bool RG = false>
 __device__ __forceinline__ void dad_prep_dispatch_s(const DadPrepArgs& a, int wave, int nwaves, int lane, int clean,
                                                     bool noisy) {
   const bool noise = a.nw != nullptr;
   if (a.f16) {
-    if (noise) dad_prep_rows<1, true, R, STOREN, S>(a, wave, nwaves, lane, clean, noisy);
-    else dad_prep_rows<0, true, R, STOREN, S>(a, wave, nwaves, lane, clean, noisy);
+    if (noise) dad_prep_rows<1, true, R, STOREN, S, RG>(a, wave, nwaves, lane, clean, noisy);
+    else dad_prep_rows<0, true, R, STOREN, S, RG>(a, wave, nwaves, lane, clean, noisy);
   } else {
-    if (noise) dad_prep_rows<1, false, R, STOREN, S>(a, wave, nwaves, lane, clean, noisy);
-    else dad_prep_rows<0, false, R, STOREN, S>(a, wave, nwaves, lane, clean, noisy);
+    if (noise) dad_prep_rows<1, false, R, STOREN, S, RG>(a, wave, nwaves, lane, clean, noisy);
+    else dad_prep_rows<0, false, R, STOREN, S, RG>(a, wave, nwaves, lane, clean, noisy);
   }
 }
-template <int R, typename S>
+template <int R, typename S, bool RG = false>
 __device__ __forceinline__ void dad_prep_dispatch_t(const DadPrepArgs& a, int wave, int nwaves, int lane, int clean,
                                                     bool noisy) {
-  if (a.src.rown != nullptr && a.g.Bn <= 64 && !a.warmup) dad_prep_dispatch_s<R, true, S>(a, wave, nwaves, lane, clean, noisy);
-  else dad_prep_dispatch_s<R, false, S>(a, wave, nwaves, lane, clean, noisy);
+  if (a.src.rown != nullptr && a.g.Bn <= 64 && !a.warmup) dad_prep_dispatch_s<R, true, S, RG>(a, wave, nwaves, lane, clean, noisy);
+  else dad_prep_dispatch_s<R, false, S, RG>(a, wave, nwaves, lane, clean, noisy);
 }
 // ... and on the rows' source type (DAD_STORE_*; wave-uniform).  The clean and the noisy store may
 // differ in type: the clean rows then go first, in a pass of their own, and the noisy rows follow in
 // theirs, so no pass holds a load under a condition and the type pairs need no instantiations of
 // their own.
-template <int R, typename S>
+template <int R, typename S, bool RG = false>
 __device__ __forceinline__ void dad_prep_clean_pass(const DadPrepArgs& a, int wave, int nwaves, int lane) {
-  if (a.f16) dad_prep_rows<0, true, R, false, S>(a, wave, nwaves, lane, 1, false);
-  else dad_prep_rows<0, false, R, false, S>(a, wave, nwaves, lane, 1, false);
+  if (a.f16) dad_prep_rows<0, true, R, false, S, RG>(a, wave, nwaves, lane, 1, false);
+  else dad_prep_rows<0, false, R, false, S, RG>(a, wave, nwaves, lane, 1, false);
 }
 // S16 = false: every source row is f32 (padded batches and f32 stores; dad_prep, dad_tail_ecda_w).
 // S16 = true: the `_s16` siblings of those kernels, launched when a part of the set comes from an
 // fp16 / bf16 store (dad_prep_s16_needed); kernels of their own, so that the f32 kernels hold the f32
 // code alone and compile to what they did before the 16-bit stores.
-template <int R, bool S16 = false>
+// RG: the ragged step's kernels (dad_prep_rows); they take the S16 form, which covers f32 stores too.
+template <int R, bool S16 = false, bool RG = false>
 __device__ __forceinline__ void dad_prep_dispatch(const DadPrepArgs& a, int wave, int nwaves, int lane) {
   if constexpr (!S16) {
     dad_prep_dispatch_t<R, float>(a, wave, nwaves, lane, a.clean, true);
@@ -238,14 +251,14 @@ __device__ __forceinline__ void dad_prep_dispatch(const DadPrepArgs& a, int wave
     const bool has_noisy = !a.warmup && a.g.Bn > 0;
     const int tn = has_noisy ? a.xn_type() : a.xc_type(), tc = a.clean ? a.xc_type() : tn;
     if (tc != tn) {
-      if (tc == DAD_STORE_F16) dad_prep_clean_pass<R, _Float16>(a, wave, nwaves, lane);
-      else if (tc == DAD_STORE_BF16) dad_prep_clean_pass<R, __bf16>(a, wave, nwaves, lane);
-      else dad_prep_clean_pass<R, float>(a, wave, nwaves, lane);
+      if (tc == DAD_STORE_F16) dad_prep_clean_pass<R, _Float16, RG>(a, wave, nwaves, lane);
+      else if (tc == DAD_STORE_BF16) dad_prep_clean_pass<R, __bf16, RG>(a, wave, nwaves, lane);
+      else dad_prep_clean_pass<R, float, RG>(a, wave, nwaves, lane);
     }
     const int clean = tc == tn ? a.clean : 0;
-    if (tn == DAD_STORE_F16) dad_prep_dispatch_t<R, _Float16>(a, wave, nwaves, lane, clean, true);
-    else if (tn == DAD_STORE_BF16) dad_prep_dispatch_t<R, __bf16>(a, wave, nwaves, lane, clean, true);
-    else dad_prep_dispatch_t<R, float>(a, wave, nwaves, lane, clean, true);
+    if (tn == DAD_STORE_F16) dad_prep_dispatch_t<R, _Float16, RG>(a, wave, nwaves, lane, clean, true);
+    else if (tn == DAD_STORE_BF16) dad_prep_dispatch_t<R, __bf16, RG>(a, wave, nwaves, lane, clean, true);
+    else dad_prep_dispatch_t<R, float, RG>(a, wave, nwaves, lane, clean, true);
   }
 }
 

@@ -112,6 +112,11 @@ struct JobMap {
   int a0, stride;
   __device__ __forceinline__ int operator()(int l) const { return a0 + l * stride; }
 };
+// the ragged encoder's jobs: local job l is entry l of the workgroup's table of dense job numbers (LDS)
+struct JobTab {
+  const int* t;
+  __device__ __forceinline__ int operator()(int l) const { return t[l]; }
+};
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {
@@ -342,8 +347,8 @@ __device__ __forceinline__ void dad_glds16x6(const char* base, uint32_t tab, uin
       : "memory", "scc");
 }
 
-template <bool TEACHER, bool F16>
-__device__ __forceinline__ void wp_loop_pp(const Ctx& C, const JobMap jm, const int nj, const int w, const int lane,
+template <bool TEACHER, bool F16, class JM>
+__device__ __forceinline__ void wp_loop_pp(const Ctx& C, const JM jm, const int nj, const int w, const int lane,
                                            char* smem, const uint32_t sbase, const bf16x8* W, const float* bias,
                                            uint32_t* vb, const DadEncodeArgs& a, const int grp) {
   using S = Shape<8>;
@@ -471,7 +476,15 @@ __device__ __forceinline__ void wp_loop_pp(const Ctx& C, const JobMap jm, const 
 
 // Roles (dad_wp_job_range): teacher workgroups run the weak slabs with the teacher's W1, student
 // workgroups the clean then the strong slabs with the student's W1, all on prepared rows.
-template <bool F16>
+// RG (encode_ws_rg.hip: dad_encode_wp[_f16]_rg, the ragged step): the job numbers are indices into the
+// live lists (dad_common.h "Ragged mode"): every workgroup builds the live prefixes from the batch's device
+// lengths in the job stages' LDS, still unused then (one block scan, no launch, no host read), takes its
+// share of the live jobs over the same nt + ns grid (dad_rg_job_range) and maps them to dense job numbers
+// in a 256-entry table; job_of, the DMA addresses, the valid bits and the partial / bits rows are the dense
+// step's.  The shares are even by live sub-slabs, as the dense step's, unless one would then exceed the
+// 256-job table (many utterances of at most 16 frames sorted together): the role's jobs are then split
+// evenly by count (dad_rg_by_slabs; every workgroup of the role reaches the same verdict).
+template <bool F16, bool RG = false>
 __device__ __forceinline__ void encode_wp_body(const DadEncodeArgs& a, char* smem) {
   constexpr int WAVES = DAD_ENC_WS_THREADS / 64;
   const Ctx C = ctx_of(a);
@@ -479,14 +492,37 @@ __device__ __forceinline__ void encode_wp_body(const DadEncodeArgs& a, char* sme
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   bool teacher;
   int j0, j1;
-  dad_wp_job_range(blockIdx.x, a.ws_nt, a.ws_ns, C.Bc, C.Tc, C.ncc, C.Bn, C.Tn, C.ncn, C.Js, teacher, j0, j1);
+  const int rg_bn = C.Js ? C.Bn : 0, rg_n = C.Bc + rg_bn;
+  int* const lps = reinterpret_cast<int*>(smem);   // RG: the live prefixes (ps, pss, pz), [rg_n + 1] each
+  int* const lpss = lps + (rg_n + 1);
+  int* const lpz = lpss + (rg_n + 1);
+  if constexpr (RG) {
+    dad_live_prefix_lds(a.src.lenc, C.Bc, C.ncc, C.Tc, a.src.lenn, rg_bn, C.ncn, C.Tn, lps, lpss, lpz);
+    // the role's split rule: a cheap bound first (block-uniform), else every range of the role, in parallel
+    const bool role_t = (int)blockIdx.x < a.ws_nt;
+    bool by_slabs = false;
+    if (!dad_rg_subs_fit(a.ws_nt, a.ws_ns, lpss, C.Bc, rg_n, role_t)) {
+      const int first = role_t ? 0 : a.ws_nt, parts = role_t ? a.ws_nt : a.ws_ns;
+      int over = 0;
+      for (int g = first + tid; g < first + parts; g += DAD_ENC_WS_THREADS) {
+        bool t;
+        int x0, x1;
+        dad_rg_job_range(g, a.ws_nt, a.ws_ns, lps, lpss, C.Bc, rg_n, false, t, x0, x1);
+        over |= x1 - x0 > DAD_ENC_WS_MAXJ;
+      }
+      by_slabs = __syncthreads_or(over) != 0;
+    }
+    dad_rg_job_range(blockIdx.x, a.ws_nt, a.ws_ns, lps, lpss, C.Bc, rg_n, by_slabs, teacher, j0, j1);
+  } else {
+    dad_wp_job_range(blockIdx.x, a.ws_nt, a.ws_ns, C.Bc, C.Tc, C.ncc, C.Bn, C.Tn, C.ncn, C.Js, teacher, j0, j1);
+  }
   const JobMap jm{j0, 1};
   const int nj = j1 - j0;
   WS_STAMP(0, DAD_PROBE_WALL());
   WS_STAMP(3, ((unsigned long long)(teacher ? 0 : 1) << 16) | (unsigned long long)(2 * nj));
   if (blockIdx.x == 0 && tid == 0 && a.pool_ready)   // (the tail launch that counts into it follows this one)
     for (int k = 0; k <= DAD_POOL_SHARDS; ++k) __hip_atomic_store(a.pool_ready + 32 * k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (nj <= 0) return;
+  if (nj <= 0 || (RG && nj > DAD_ENC_WS_MAXJ)) return;   // (RG, nj > the table: not reached, dad_rg_by_slabs; no write past it)
   const uint32_t sbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   // valid bits of every job (bit r = row r of the 32-row slab is a frame of the utterance)
   uint32_t* vb = reinterpret_cast<uint32_t*>(smem + kOffPVB);
@@ -500,17 +536,34 @@ __device__ __forceinline__ void encode_wp_body(const DadEncodeArgs& a, char* sme
   const bf16x8* W = reinterpret_cast<const bf16x8*>(teacher ? a.w1h_teacher : a.w1h_student);
   const float* bias = teacher ? a.b1_teacher : a.b1_student;
   WS_STAMP(1, DAD_PROBE_WALL());
-  if (teacher) wp_loop_pp<true, F16>(C, jm, nj, w, lane, smem, sbase, W, bias, vb, a, grp);
-  else wp_loop_pp<false, F16>(C, jm, nj, w, lane, smem, sbase, W, bias, vb, a, grp);
+  if constexpr (!RG) {
+    if (teacher) wp_loop_pp<true, F16>(C, jm, nj, w, lane, smem, sbase, W, bias, vb, a, grp);
+    else wp_loop_pp<false, F16>(C, jm, nj, w, lane, smem, sbase, W, bias, vb, a, grp);
+  } else {
+    int* const jt = reinterpret_cast<int*>(smem + kLdsP);
+    if (tid < nj) jt[tid] = dad_rg_dense_job(lps, C.Bc, rg_n, C.ncc, C.ncn, teacher, j0 + tid);
+    __syncthreads();   // the table is complete and the prefixes are read: the stages are free for the DMA
+    const JobTab jtab{jt};
+    if (teacher) wp_loop_pp<true, F16>(C, jtab, nj, w, lane, smem, sbase, W, bias, vb, a, grp);
+    else wp_loop_pp<false, F16>(C, jtab, nj, w, lane, smem, sbase, W, bias, vb, a, grp);
+  }
   WS_STAMP(2, DAD_PROBE_WALL());
 }
 
-#define DAD_WP_KERNEL(name, F16)                                                     \
+// (RG: the job table behind the dense kernel's LDS)
+static_assert(kLdsP + 4 * DAD_ENC_WS_MAXJ <= 160 * 1024, "LDS budget (ragged)");
+static_assert(3 * 4 * (2 * DAD_MAX_BATCH + 1) <= kOffPVB, "the live prefixes fit the job stages");
+#define DAD_WP_KERNEL(name, F16, RG)                                                 \
   __global__ __launch_bounds__(DAD_ENC_WS_THREADS, 1) void name(DadEncodeArgs a) {   \
     DAD_GUARD_BLOCK(DAD_ENC_WS_THREADS);                                             \
-    __shared__ __attribute__((aligned(16))) char smem[kLdsP];                        \
-    encode_wp_body<F16>(a, smem);                                                    \
+    __shared__ __attribute__((aligned(16))) char smem[kLdsP + (RG ? 4 * DAD_ENC_WS_MAXJ : 0)]; \
+    encode_wp_body<F16, RG>(a, smem);                                                \
   }
-DAD_WP_KERNEL(dad_encode_wp, false)
-DAD_WP_KERNEL(dad_encode_wp_f16, true)
+#ifndef DAD_ENC_WS_RG
+DAD_WP_KERNEL(dad_encode_wp, false, false)
+DAD_WP_KERNEL(dad_encode_wp_f16, true, false)
+#else
+DAD_WP_KERNEL(dad_encode_wp_rg, false, true)
+DAD_WP_KERNEL(dad_encode_wp_f16_rg, true, true)
+#endif
 #undef DAD_WP_KERNEL

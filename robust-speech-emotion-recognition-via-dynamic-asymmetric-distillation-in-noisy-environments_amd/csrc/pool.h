@@ -38,7 +38,10 @@ __device__ __forceinline__ void pool_st1(T* p, T v) {
 }
 
 // pool item blk (one wave, lane = 0..63): what one dad_pool workgroup does
-template <bool SC1>
+// RG (the ragged step's kernels): the encoder wrote the partials of the utterance's live slabs only
+// (c < ceil(len_b / 32), len_b from a.lenc / a.lenn), so only those are summed, in the same slab order;
+// the dead slabs' partials of the dense step are exact zeros, so the sums are the same bits.
+template <bool SC1, bool RG = false>
 __device__ __forceinline__ void pool_item(const DadPoolArgs& a, const int blk, const int lane) {
   const DadGeom& g = a.g;
   const int kind = blk < g.Bc ? 0 : (blk < g.Bc + g.Bn ? 1 : 2);   // clean, teacher (weak), student (strong)
@@ -47,7 +50,12 @@ __device__ __forceinline__ void pool_item(const DadPoolArgs& a, const int blk, c
   const int T = noisy ? g.Tn : g.Tc;
   const uint8_t* pad = (noisy ? a.mn : a.mc) + (size_t)b * T;
   const size_t nsc = (size_t)g.Bc * g.ncc, nsn = (size_t)g.Bn * g.ncn;
-  const int nc = noisy ? g.ncn : g.ncc;
+  int nc = noisy ? g.ncn : g.ncc;
+  int clast = nc - 1;      // slab index the batched loads are clamped to
+  if constexpr (RG) {
+    nc = dad_live_slabs((noisy ? a.lenn : a.lenc)[b], nc);
+    clast = max(nc - 1, 0);   // (no live slab: slab 0's address, loaded and selected away)
+  }
   const size_t slab0 = kind == 0 ? (size_t)b * g.ncc : (kind == 1 ? nsc + (size_t)b * g.ncn : nsc + nsn + (size_t)b * g.ncn);
   const size_t cslab0 = noisy ? nsc + (size_t)b * g.ncn : (size_t)b * g.ncc;   // active counts (clean / strong)
   const int erow = kind == 0 ? b : (kind == 1 ? g.Bc + b : g.Bc + g.Bn + b);
@@ -64,7 +72,7 @@ __device__ __forceinline__ void pool_item(const DadPoolArgs& a, const int blk, c
   f32x4 ps[POOL_BATCH], pc[POOL_BATCH];
 #pragma unroll
   for (int k = 0; k < POOL_BATCH; ++k) {
-    const int c = min(k, nc - 1);
+    const int c = min(k, clast);
     ps[k] = *reinterpret_cast<const f32x4*>(a.part_sum + (slab0 + c) * DAD_H + h0);
     pc[k] = *reinterpret_cast<const f32x4*>(a.part_cnt + (cslab0 + c) * DAD_H + h0);
   }
@@ -83,7 +91,7 @@ __device__ __forceinline__ void pool_item(const DadPoolArgs& a, const int blk, c
   for (int c0 = POOL_BATCH; c0 < nc; c0 += POOL_BATCH) {   // utterances past 512 frames
 #pragma unroll
     for (int k = 0; k < POOL_BATCH; ++k) {
-      const int c = min(c0 + k, nc - 1);
+      const int c = min(c0 + k, clast);
       ps[k] = *reinterpret_cast<const f32x4*>(a.part_sum + (slab0 + c) * DAD_H + h0);
       pc[k] = *reinterpret_cast<const f32x4*>(a.part_cnt + (cslab0 + c) * DAD_H + h0);
     }

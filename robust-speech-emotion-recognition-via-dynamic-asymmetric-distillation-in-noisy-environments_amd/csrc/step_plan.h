@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "dad_kernels.h"
 
@@ -18,6 +19,7 @@ inline int check_cfg(const dad_config* c) {
   if (c->precision != DAD_PREC_FP32 && !dad_prec16(c->precision)) return DAD_E_ARG;
   if (c->rng_mode != DAD_RNG_EXPLICIT && c->rng_mode != DAD_RNG_COUNTER) return DAD_E_ARG;
   if (c->dp_world < 1) return DAD_E_ARG;
+  if (c->ragged && !dad_prec16(c->precision)) return DAD_E_UNSUPPORTED;   // (ragged mode: the 16-bit store-fed steps)
   return DAD_OK;
 }
 
@@ -37,6 +39,13 @@ inline int check_batch_dtypes(const dad_config* c, const dad_batch* b) {
   if ((!b->rowc && b->xc_dtype != DAD_STORE_F32) || (!b->rown && b->xn_dtype != DAD_STORE_F32)) return DAD_E_ARG;
   if ((b->xc_dtype != DAD_STORE_F32 || b->xn_dtype != DAD_STORE_F32) && !dad_prec16(c->precision))
     return DAD_E_UNSUPPORTED;
+  return DAD_OK;
+}
+// Ragged mode reads the lengths of every batch side that is present: both must be store batches.
+inline int check_ragged_batch(const dad_config* c, const dad_batch* b) {
+  if (!c->ragged) return DAD_OK;
+  if (!b->rowc || !b->lenc) return DAD_E_ARG;
+  if ((b->xn || !c->warmup) && (!b->rown || !b->lenn)) return DAD_E_ARG;
   return DAD_OK;
 }
 // DAD_RNG_EXPLICIT: the augmentation's four draws of a noisy batch
@@ -154,6 +163,8 @@ inline bool can_prepare_ahead(const dad_config* cfg, int max_splits, const dad_c
   if (ncfg->B != cfg->B || ncfg->T != cfg->T || ncfg->Bn != cfg->Bn || ncfg->Tn != cfg->Tn) return false;
   if (((ncfg->counter ^ cfg->counter) & 1u) == 0) return false;
   if (max_splits_of(ncfg) != max_splits) return false;
+  // a set prepared ragged holds its live rows only: a ragged step reads it, and a dense step a dense set
+  if ((ncfg->ragged != 0) != (cfg->ragged != 0) || check_ragged_batch(ncfg, nbt) != DAD_OK) return false;
   // (a store of any DAD_STORE_* type qualifies: the preparation reads 16-bit rows in place; the callers
   // report check_batch_dtypes' code for a batch it refuses)
   if (check_batch_dtypes(ncfg, nbt) != DAD_OK) return false;
@@ -226,4 +237,49 @@ inline StepPlan plan_step(const dad_config* cfg, const dad_config* next_cfg, con
     p.reduce_grid = DAD_REDUCE_BLOCKS;
   }
   return p;
+}
+
+// dad_step_ragged_plan (dad.h): the shares of a ragged step's live slabs, from host copies of the lengths,
+// by the functions the `_rg` kernels call on the device lengths (dad_common.h "Ragged mode"): the encoder's
+// grid is wp_split's and the split count splits_of's, as for the dense step (neither depends on the
+// lengths).  (A diagnostic: it allocates its three prefix arrays.)
+inline int ragged_plan(const dad_config* cfg, const int32_t* lenc, const int32_t* lenn, int cus, dad_ragged_plan* out) {
+  const DadGeom G = geom_of(cfg);
+  const int Bn = cfg->warmup ? 0 : G.Bn, n = G.Bc + Bn;
+  int nt = 0, ns = 0;
+  const int rc = wp_split(G, Bn, cus, nt, ns);
+  if (rc) return rc;
+  const int splits = splits_of(cfg);
+  out->enc_grid = nt + ns;
+  out->splits = splits;
+  if (!out->enc || !out->split || out->enc_capacity < nt + ns || out->split_capacity < splits) return DAD_E_ARG;
+  std::vector<int> pre(3 * (size_t)(n + 1));
+  int* ps = pre.data();
+  int* pss = ps + (n + 1);
+  int* pz = pss + (n + 1);
+  dad_live_prefix_host(lenc, G.Bc, G.ncc, G.Tc, lenn, Bn, G.ncn, G.Tn, ps, pss, pz);
+  out->live_clean = ps[G.Bc];
+  out->live_noisy = ps[n] - ps[G.Bc];
+  out->max_enc_range = 0;
+  const bool by_t = dad_rg_by_slabs(nt, ns, ps, pss, G.Bc, n, true, DAD_ENC_WS_MAXJ);
+  const bool by_s = dad_rg_by_slabs(nt, ns, ps, pss, G.Bc, n, false, DAD_ENC_WS_MAXJ);
+  for (int wg = 0; wg < nt + ns; ++wg) {
+    bool t = false;
+    int j0 = 0, j1 = 0;
+    dad_rg_job_range(wg, nt, ns, ps, pss, G.Bc, n, wg < nt ? by_t : by_s, t, j0, j1);
+    out->enc[3 * wg] = t ? 1 : 0;
+    out->enc[3 * wg + 1] = j0;
+    out->enc[3 * wg + 2] = j1 - j0;
+    out->max_enc_range = std::max(out->max_enc_range, j1 - j0);
+  }
+  out->max_split_utts = 0;
+  for (int s = 0; s < splits; ++s) {
+    int s0 = 0, s1 = 0;
+    dad_wg_share(ps[n], splits, s, s0, s1);
+    out->split[2 * s] = s0;
+    out->split[2 * s + 1] = s1;
+    if (s0 < s1)
+      out->max_split_utts = std::max(out->max_split_utts, pz[dad_live_find(ps, n, s1 - 1)] - pz[dad_live_find(ps, n, s0)] + 1);
+  }
+  return DAD_OK;
 }

@@ -24,6 +24,11 @@ __global__ __launch_bounds__(DAD_POOL_THREADS) void dad_pool(DadPoolArgs a) {
   DAD_GUARD_BLOCK(DAD_POOL_THREADS);
   pool_item<false>(a, (int)blockIdx.x, (int)threadIdx.x);
 }
+// the ragged step's pooling: live slabs only (pool.h, RG)
+__global__ __launch_bounds__(DAD_POOL_THREADS) void dad_pool_rg(DadPoolArgs a) {
+  DAD_GUARD_BLOCK(DAD_POOL_THREADS);
+  pool_item<false, true>(a, (int)blockIdx.x, (int)threadIdx.x);
+}
 
 // ------------------------------------------------------------------------------ tail
 // Latency design (one workgroup, ~30 dependent phases): every global input is requested at

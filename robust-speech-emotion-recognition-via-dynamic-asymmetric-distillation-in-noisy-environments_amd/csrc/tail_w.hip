@@ -978,11 +978,19 @@ __device__ __forceinline__ void ecda_block_w(const DadEcdaArgs& a, const DadTail
 // tail_w_s16.hip compiles this file again as dad_tail_ecda_w_s16: the same launch with the preparation
 // reading rows of an fp16 / bf16 store (dad_prep_dispatch, S16).  A kernel and a unit of its own, so
 // that this one holds the f32 preparation alone and compiles to what it did before the 16-bit stores.
-#ifdef DAD_TAIL_W_S16
+// tail_w_rg.hip compiles it a third time as dad_tail_ecda_w_rg, the ragged step's launch: the pooling sums
+// live slabs only and the preparation skips the rows of dead slabs (pool.h, dad_prep.h: RG), the rows read
+// in the store's own type.
+#if defined(DAD_TAIL_W_RG)
+#define TAIL_W_KERNEL dad_tail_ecda_w_rg
+#define DAD_TAIL_W_S16 1
+#elif defined(DAD_TAIL_W_S16)
 #define TAIL_W_KERNEL dad_tail_ecda_w_s16
+#define DAD_TAIL_W_RG 0
 #else
 #define TAIL_W_KERNEL dad_tail_ecda_w
 #define DAD_TAIL_W_S16 0
+#define DAD_TAIL_W_RG 0
 #endif
 __global__ __launch_bounds__(TAIL_THREADS) void TAIL_W_KERNEL(DadTailArgs ta, DadEcdaArgs ca, DadPrepArgs pa,
                                                                 DadPoolArgs pl) {
@@ -999,14 +1007,14 @@ __global__ __launch_bounds__(TAIL_THREADS) void TAIL_W_KERNEL(DadTailArgs ta, Da
     const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int nx = (int)gridDim.x - 1 - DAD_C, xb = (int)blockIdx.x - 1 - DAD_C;
     for (int i = xb + nx * w; i < nitems; i += nx * kWaves) {
-      pool_item<true>(pl, i, (int)threadIdx.x & 63);
+      pool_item<true, DAD_TAIL_W_RG>(pl, i, (int)threadIdx.x & 63);
       pool_publish(pl.ready, (int)threadIdx.x & 63);
     }
     if (!pa.x16) return;
 #ifdef DAD_PROBE_STAMPS
     if ((threadIdx.x & 63) == 0 && xb < 256) prep_stamps[2 * (xb * kWaves + w)] = DAD_PROBE_WALL();
 #endif
-    dad_prep_dispatch<2, DAD_TAIL_W_S16>(pa, xb * kWaves + w, nx * kWaves, (int)threadIdx.x & 63);
+    dad_prep_dispatch<2, DAD_TAIL_W_S16, DAD_TAIL_W_RG>(pa, xb * kWaves + w, nx * kWaves, (int)threadIdx.x & 63);
 #ifdef DAD_PROBE_STAMPS
     if (threadIdx.x == 0) atomicMax(&ecda_stamps[DAD_C * ECDA_SLOTS + 15], (unsigned long long)DAD_PROBE_WALL());
     if ((threadIdx.x & 63) == 0 && xb < 256) prep_stamps[2 * (xb * kWaves + w) + 1] = DAD_PROBE_WALL();

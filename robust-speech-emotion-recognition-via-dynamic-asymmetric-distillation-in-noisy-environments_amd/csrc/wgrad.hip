@@ -293,6 +293,7 @@ __device__ __forceinline__ void wgrad_f32_mode(const DadWgradArgs& a, const DadR
   else wgrad_f32_store<EXPLICIT, F32_FUSED, false>(a, ra, Gs);
 }
 
+#ifndef DAD_WGRAD_RG   // (wgrad_rg.hip holds the ragged siblings of the direct kernels only)
 __global__ __launch_bounds__(DAD_WGRAD_THREADS) void dad_wgrad_f32(DadWgradArgs a, DadReduceArgs ra) {
   DAD_GUARD_BLOCK(DAD_WGRAD_THREADS);
   static_assert(DAD_WGRAD_THREADS == DAD_H, "dad_wgrad_f32: thread = hidden unit for the G tile");
@@ -300,6 +301,7 @@ __global__ __launch_bounds__(DAD_WGRAD_THREADS) void dad_wgrad_f32(DadWgradArgs 
   if (a.ns) wgrad_f32_mode<true>(a, ra, Gs);
   else wgrad_f32_mode<false>(a, ra, Gs);
 }
+#endif
 
 // ------------------------------------------------------- FP16 / BF16 (throughput modes)
 // Direct split-K GEMM after the losses: dW1 = sum_rows G[row]^T x[row] with
@@ -388,6 +390,7 @@ struct WgdLane {
 // A load reads its slab's entry with v_readlane, so no cursor arithmetic runs per slab.
 struct WgdTable {
   int row0, info;
+  int sd;   // RG: the slab's dense index (its row of the ReLU' mask buffer)
 };
 
 __device__ __forceinline__ WgdTable wgd_table(const DadGeom& g, int s, int u0) {
@@ -400,6 +403,23 @@ __device__ __forceinline__ WgdTable wgd_table(const DadGeom& g, int s, int u0) {
   WgdTable t;
   t.row0 = (br ? g.Bc * g.Tc + b * T : b * T) + c * DAD_SLAB;
   t.info = (((br ? g.Bc + b : b) - u0) << 8) | min(T - c * DAD_SLAB, DAD_SLAB);
+  t.sd = s;
+  return t;
+}
+// RG (the ragged step, wgrad_rg.hip): the lane's slab is live index k of the student list (live clean, then
+// live strong slabs; ps / pz: the live prefixes of dad_common.h over the n list utterances, in LDS).  The
+// utterance slot counts the utterances WITH a live slab from the split's first on (pz - zfirst), by order
+// of appearance: utterances of length 0 between two live ones take no slot of the LDS dL/de table.
+__device__ __forceinline__ WgdTable wgd_table_rg(const DadGeom& g, const int* ps, const int* pz, int n, int k,
+                                                 int zfirst) {
+  const int u = dad_live_find(ps, n, k), c = k - ps[u];
+  const bool br = u >= g.Bc;
+  const int b = br ? u - g.Bc : u;
+  const int T = br ? g.Tn : g.Tc;
+  WgdTable t;
+  t.row0 = (br ? g.Bc * g.Tc + b * T : b * T) + c * DAD_SLAB;
+  t.info = ((pz[u] - zfirst) << 8) | min(T - c * DAD_SLAB, DAD_SLAB);
+  t.sd = br ? g.Bc * g.ncc + b * g.ncn + c : b * g.ncc + c;
   return t;
 }
 
@@ -408,18 +428,23 @@ __device__ __forceinline__ WgdTable wgd_table(const DadGeom& g, int s, int u0) {
 // clean + strong parts read 0, rows past the utterance are the next utterance's prepared rows; both
 // are finite and meet mask bits 0, so no clamp runs per slab) and this lane's two row masks
 // (buffer loads at the slab's scalar offset)
+// RG: the rows past the padded length T read 0 as well (in the dense step they are the next utterance's
+// prepared rows; a ragged set holds none for an utterance without frames), and the mask words sit at the
+// slab's dense index.
+template <bool RG = false>
 __device__ __forceinline__ void wgd_load(const DadWgradArgs& a, const WgdTable& tab, int j, int sfirst,
                                           const WgdLane& ln, WgdSlab& r) {
   const int row0 = __builtin_amdgcn_readlane(tab.row0, j);
   const int info = __builtin_amdgcn_readlane(tab.info, j);
   r.ul = info >> 8;
   r.nvalid = 0;
-  const int n = min(__builtin_amdgcn_readfirstlane(ln.nrows) - row0, DAD_SLAB);   // (uniform: SGPR rsrc)
+  int n = min(__builtin_amdgcn_readfirstlane(ln.nrows) - row0, DAD_SLAB);   // (uniform: SGPR rsrc)
+  if constexpr (RG) n = min(n, info & 0xff);
   const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.xs16 + (size_t)row0 * DAD_D), (short)0,
                                                     n * DAD_D * 2, 0x00020000);
   r.x = __builtin_amdgcn_raw_buffer_load_b128(rx, ln.xoff, 0, 0);
   const auto rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(a.bits), (short)0, -1, 0x00020000);
-  const int soff = (sfirst + WGD_GROUPS * j) * DAD_H * 4;
+  const int soff = (RG ? __builtin_amdgcn_readlane(tab.sd, j) : sfirst + WGD_GROUPS * j) * DAD_H * 4;
   r.mw[0] = __builtin_amdgcn_raw_buffer_load_b32(rb, ln.moff, soff, 0);
   r.mw[1] = __builtin_amdgcn_raw_buffer_load_b32(rb, ln.moff + 128, soff, 0);
 }
@@ -532,13 +557,22 @@ __device__ __forceinline__ int wgd_f16_exp(float max_abs) {
 // resource per row, the lane's column offset a loop-invariant register, the three 16-B / 8-B
 // pieces at immediate offsets; non-temporal loads as in dad_prep_clean_load.  S: the clean rows'
 // source type (DadSrc; a 16-bit store row is 1536 B, its pieces 8 B at 512 k + 8 lane)
-template <bool STORE, typename S>
+// RG (ragged next batch, a store batch): a clean row of a dead slab, t >= 32 ceil(len_b / 32), gets a
+// resource of 0 bytes for its load and for its store: the loads return 0 without a memory access and the
+// stores are dropped by the range check, with no condition inside the pipelined loop.
+__device__ __forceinline__ bool wgd_cp_live(const DadPrepArgs& a, int uc, const StoreRowsW& sr) {
+  const int b = sr.tmag ? (int)__umulhi((uint32_t)uc, sr.tmag) : uc;
+  const int t = uc - b * a.g.Tc;
+  return t < DAD_SLAB * dad_live_slabs(__builtin_amdgcn_readlane(sr.len, b), a.g.ncc);
+}
+template <bool STORE, typename S, bool RG = false>
 __device__ __forceinline__ void wgd_cp_load(const DadPrepArgs& a, int u, uint32_t loff, typename DadSrc<S>::raw (&v)[3],
                                             const StoreRowsW& sr) {
   const int uc = min(u, a.g.Bc * a.g.Tc - 1);
   const size_t srow = dad_clean_src_row<STORE>(a, uc, sr);
+  const int bytes = !RG || wgd_cp_live(a, uc, sr) ? DAD_D * (int)sizeof(S) : 0;
   const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<S*>(static_cast<const S*>(a.xc) + srow * DAD_D), (short)0,
-                                                   DAD_D * (int)sizeof(S), 0x00020000);
+                                                   bytes, 0x00020000);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     if constexpr (sizeof(S) == 4)
@@ -547,11 +581,12 @@ __device__ __forceinline__ void wgd_cp_load(const DadPrepArgs& a, int u, uint32_
       v[k] = __builtin_amdgcn_raw_buffer_load_b64(r, loff + 512 * k, 0, 2);
   }
 }
-template <bool F16, typename S>
+template <bool F16, typename S, bool RG = false>
 __device__ __forceinline__ void wgd_cp_store(const DadPrepArgs& a, int u, uint32_t soff,
-                                             const typename DadSrc<S>::raw (&v)[3]) {
+                                             const typename DadSrc<S>::raw (&v)[3], const StoreRowsW& sr = StoreRowsW{}) {
   const int uc = min(u, a.g.Bc * a.g.Tc - 1);
-  const auto r = __builtin_amdgcn_make_buffer_rsrc(a.x16 + (size_t)uc * DAD_D, (short)0, DAD_D * 2, 0x00020000);
+  const int bytes = !RG || wgd_cp_live(a, uc, sr) ? DAD_D * 2 : 0;
+  const auto r = __builtin_amdgcn_make_buffer_rsrc(a.x16 + (size_t)uc * DAD_D, (short)0, bytes, 0x00020000);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const uint2 o = dad_src_pack<F16, S>(v[k]);
@@ -569,10 +604,13 @@ constexpr int WGD_NBUF = 4;
 // block (an HBM miss under this load takes about as long as NB rounds); the rows left after the
 // loop follow it.  CP = 1: padded next batch; CP = 2: store batch (Bc <= 64), source rows through
 // the utterance table held in registers (StoreRowsW), rows of type SC (a 16-bit store is read in place).
-template <bool F16, int CP, typename SC = float>
+// RG (the ragged step): [s0, s1) is a range of the live student list, lps / lpz its live prefixes over the
+// ln_ list utterances (in the x tiles' LDS, read in the prologue only, before the first slab is staged).
+template <bool F16, int CP, typename SC = float, bool RG = false>
 __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceArgs& ra, int s0, int s1, int dbase,
                                          float* outf, uint16_t* Xt, const uint4* lut, uint16_t* gs, float* red,
-                                         const DadPrepArgs& pc, int gw, int GW) {
+                                         const DadPrepArgs& pc, int gw, int GW, const int* lps = nullptr,
+                                         const int* lpz = nullptr, int ln_ = 0) {
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
   const int grp = __builtin_amdgcn_readfirstlane(tid >> 8);
@@ -596,7 +634,19 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
     const int nround = (n + WGD_GROUPS - 1) / WGD_GROUPS;
     const int mine = (n - grp + WGD_GROUPS - 1) / WGD_GROUPS;   // group 1 may have one slab fewer
     const int cntmin = n / WGD_GROUPS;
-    const int u0 = wgd_utt(g, s0), nu = wgd_utt(g, s1 - 1) - u0 + 1;
+    // RG: the split's utterances are those with a live slab from its first slab's on, slot i = the i-th
+    // of them (lane i of uslot; at most WGD_MAXU: a range holds at most WGD_MAXU slabs)
+    int u0, nu, zfirst = 0, uslot = 0;
+    if constexpr (RG) {
+      zfirst = lpz[dad_live_find(lps, ln_, s0)];
+      nu = lpz[dad_live_find(lps, ln_, s1 - 1)] - zfirst + 1;
+      u0 = 0;
+      uslot = dad_live_find(lpz, ln_, zfirst + min(lane, nu - 1));
+    } else {
+      u0 = wgd_utt(g, s0);
+      nu = wgd_utt(g, s1 - 1) - u0 + 1;
+    }
+    auto utt = [&](int i) { return RG ? __builtin_amdgcn_readlane(uslot, i) : u0 + i; };   // (i wave-uniform)
     uint16_t* Xg = Xt + grp * (WGD_NBUF * DAD_SLAB * WGD_XP);   // this group's WGD_NBUF LDS buffers
     // dL/de_u[h] / max(1, len_u) of this split's utterances (thread = h of each group) as 16-bit;
     // the host bounds a split to WGD_MAXU slabs, hence utterances.  In each batch of eight
@@ -619,14 +669,20 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
     for (int c = 0; c < 4; ++c) w2[c] = ra.student[DAD_OFF_W2 + c * DAD_H + hh];
 #pragma unroll
     for (int k = 0; k < KL; ++k) {
-      const int u = u0 + min(slot(k), nu - 1);
+      const int u = utt(min(slot(k), nu - 1));
       ec0[k] = ra.ge_ecda[(size_t)u * DAD_H + hh];
       gz0[k] = *reinterpret_cast<const f32x4*>(ra.gzb + (size_t)u * DAD_C);
       ef0[k] = ra.eflag[u];
       vl0[k] = ra.vlen[u];
     }
     const int sfirst = s0 + grp;
-    const WgdTable tab = wgd_table(g, min(sfirst + WGD_GROUPS * lane, s1 - 1), u0);
+    WgdTable tab;
+    if constexpr (RG) {
+      tab = wgd_table_rg(g, lps, lpz, ln_, min(sfirst + WGD_GROUPS * lane, s1 - 1), zfirst);
+      __syncthreads();   // every wave has read the prefixes: the x tiles may be staged
+    } else {
+      tab = wgd_table(g, min(sfirst + WGD_GROUPS * lane, s1 - 1), u0);
+    }
     WgdLane ln;
     {
       const int t = tid & 255;
@@ -643,7 +699,7 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
     // loads are unconditional (slab index clamped at the group's last slab): conditional
     // loads make the compiler merge the paths' pending counts into a vmcnt(0) drain
 #pragma unroll
-    for (int k = 0; k < WGD_DEPTH; ++k) wgd_load(a, tab, min(k, jlast), sfirst, ln, r[k]);
+    for (int k = 0; k < WGD_DEPTH; ++k) wgd_load<RG>(a, tab, min(k, jlast), sfirst, ln, r[k]);
     const unsigned long long ta = WGD_CLK();
     // the table: the first batch's values stay in registers (v0); FP16 takes the row's largest
     // |v| first (a second pass recomputes later batches), then writes the scaled values
@@ -652,7 +708,7 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
       auto batch = [&](int ul0, float (&v)[KL]) {
 #pragma unroll
         for (int k = 0; k < KL; ++k) {   // the batch's loads in flight (index clamped)
-          const int u = u0 + min(ul0 + slot(k), nu - 1);
+          const int u = utt(min(ul0 + slot(k), nu - 1));
           v[k] = ul0 == 0 ? fused_ge1_v<EX>(ra, g.Bc, u, hh, w2, gz0[k], ef0[k], ec0[k]) / fmaxf(vl0[k], 1.0f)
                           : fused_ge1<EX>(ra, g.Bc, u, hh, w2) / fmaxf(ra.vlen[u], 1.0f);
         }
@@ -706,7 +762,7 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
       mwq[q][1] = r[q].mw[1];
     }
 #pragma unroll
-    for (int q = 0; q < SD; ++q) wgd_load(a, tab, min(WGD_DEPTH + q, jlast), sfirst, ln, r[q]);
+    for (int q = 0; q < SD; ++q) wgd_load<RG>(a, tab, min(WGD_DEPTH + q, jlast), sfirst, ln, r[q]);
     const unsigned long long tc = WGD_CLK();
     __syncthreads();
     t1 = WGD_CLK();
@@ -729,7 +785,7 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
       ulq[k % SD] = r[nk].ul;
       mwq[k % SD][0] = r[nk].mw[0];
       mwq[k % SD][1] = r[nk].mw[1];
-      wgd_load(a, tab, min(jr + SD + WGD_DEPTH, jlast), sfirst, ln, r[nk]);
+      wgd_load<RG>(a, tab, min(jr + SD + WGD_DEPTH, jlast), sfirst, ln, r[nk]);
       __builtin_amdgcn_sched_barrier(0);
       if (comp) F = wgd_finish(R);
       const unsigned long long c1 = WGD_CLK();
@@ -757,16 +813,16 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
           if (k == 0) {
             // the rows loaded two blocks (2 NB rounds) ago, then this block's two
             if (pend2) {
-              wgd_cp_store<F16, SC>(pc, prow - 4 * GW, cpsoff, po[0]);
-              wgd_cp_store<F16, SC>(pc, prow - 3 * GW, cpsoff, po[1]);
+              wgd_cp_store<F16, SC, RG>(pc, prow - 4 * GW, cpsoff, po[0], srw);
+              wgd_cp_store<F16, SC, RG>(pc, prow - 3 * GW, cpsoff, po[1], srw);
             }
 #pragma unroll
             for (int q = 0; q < 2; ++q)
 #pragma unroll
               for (int e = 0; e < 3; ++e) po[q][e] = pv[q][e];
             pend2 = pending;
-            wgd_cp_load<CP == 2, SC>(pc, prow, cploff, pv[0], srw);
-            wgd_cp_load<CP == 2, SC>(pc, prow + GW, cploff, pv[1], srw);
+            wgd_cp_load<CP == 2, SC, RG>(pc, prow, cploff, pv[0], srw);
+            wgd_cp_load<CP == 2, SC, RG>(pc, prow + GW, cploff, pv[1], srw);
             prow += 2 * GW;
             pending = true;
           }
@@ -781,16 +837,16 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
     if (nround - 1 < mine) wgd_mma<F16>(F, acc);
     if constexpr (CP) {
       if (pend2) {
-        wgd_cp_store<F16, SC>(pc, prow - 4 * GW, cpsoff, po[0]);
-        wgd_cp_store<F16, SC>(pc, prow - 3 * GW, cpsoff, po[1]);
+        wgd_cp_store<F16, SC, RG>(pc, prow - 4 * GW, cpsoff, po[0], srw);
+        wgd_cp_store<F16, SC, RG>(pc, prow - 3 * GW, cpsoff, po[1], srw);
       }
       if (pending) {
-        wgd_cp_store<F16, SC>(pc, prow - 2 * GW, cpsoff, pv[0]);
-        wgd_cp_store<F16, SC>(pc, prow - GW, cpsoff, pv[1]);
+        wgd_cp_store<F16, SC, RG>(pc, prow - 2 * GW, cpsoff, pv[0], srw);
+        wgd_cp_store<F16, SC, RG>(pc, prow - GW, cpsoff, pv[1], srw);
       }
       for (; prow < pc.g.Bc * pc.g.Tc; prow += GW) {   // the rows the loop left
-        wgd_cp_load<CP == 2, SC>(pc, prow, cploff, pv[0], srw);
-        wgd_cp_store<F16, SC>(pc, prow, cpsoff, pv[0]);
+        wgd_cp_load<CP == 2, SC, RG>(pc, prow, cploff, pv[0], srw);
+        wgd_cp_store<F16, SC, RG>(pc, prow, cpsoff, pv[0], srw);
       }
     }
     t2 = WGD_CLK();
@@ -798,8 +854,8 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
     const StoreRowsW srw = CP == 2 ? dad_store_rows_w(pc, lane) : StoreRowsW{};
     for (int prow = gw; prow < pc.g.Bc * pc.g.Tc; prow += GW) {
       CpRaw pv[3];
-      wgd_cp_load<CP == 2, SC>(pc, prow, cploff, pv, srw);
-      wgd_cp_store<F16, SC>(pc, prow, cpsoff, pv);
+      wgd_cp_load<CP == 2, SC, RG>(pc, prow, cploff, pv, srw);
+      wgd_cp_store<F16, SC, RG>(pc, prow, cpsoff, pv, srw);
     }
   }
   const int kh = lane >> 5;
@@ -865,10 +921,20 @@ struct __attribute__((aligned(16))) WgdSmem {
   } a;
 };
 
-__device__ double extra_block(const DadReduceArgs& a, int e, int tid, float (*xs)[16][6]);
+// (a definition per unit: device code is linked per unit)
+#ifdef DAD_WGRAD_RG
+#define WGD_XLINK static
+#else
+#define WGD_XLINK
+#endif
+WGD_XLINK __device__ double extra_block(const DadReduceArgs& a, int e, int tid, float (*xs)[16][6]);
 
 
-template <bool F16, int CP>
+// RG (wgrad_rg.hip, the ragged step): a split's range is its share of the LIVE student list (wg_range's
+// formula on the live count: the host chose `splits` from the dense count, so a share holds at most
+// WGD_MAXU slabs); the live prefixes are built from the batch's device lengths in the x tiles' LDS.  A
+// split whose share is empty writes a zero partial.
+template <bool F16, int CP, bool RG = false>
 __device__ __forceinline__ void wgrad_direct_body(const DadWgradArgs& a, const DadReduceArgs& ra, const DadPrepArgs& pc) {
   __shared__ WgdSmem S;
   __shared__ __attribute__((aligned(16))) uint16_t gs[WGD_MAXU * DAD_H];
@@ -903,16 +969,40 @@ __device__ __forceinline__ void wgrad_direct_body(const DadWgradArgs& a, const D
     return;
   }
   const int split = tile / WGD_NDB, dblk = tile - split * WGD_NDB;
-  const int total = wg_total(a);
-  const int per = (total + a.splits - 1) / a.splits;
-  const int s0 = split * per, s1 = min(total, s0 + per);
+  int s0, s1;
+  const int rg_bn = a.warmup ? 0 : a.g.Bn, rg_n = a.g.Bc + rg_bn;
+  int* const lps = reinterpret_cast<int*>(S.a.xt);
+  int* const lpss = lps + (rg_n + 1);
+  int* const lpz = lpss + (rg_n + 1);
+  if constexpr (RG) {
+    static_assert(3 * 4 * (2 * DAD_MAX_BATCH + 1) <= sizeof(S.a), "the live prefixes fit the x tiles");
+    dad_live_prefix_lds(a.src.lenc, a.g.Bc, a.g.ncc, a.g.Tc, a.src.lenn, rg_bn, a.g.ncn, a.g.Tn, lps, lpss, lpz);
+    dad_wg_share(lps[rg_n], a.splits, split, s0, s1);
+  } else {
+    const int total = wg_total(a);
+    const int per = (total + a.splits - 1) / a.splits;
+    s0 = split * per;
+    s1 = min(total, s0 + per);
+  }
   wgd_lut(S.lut);   // (the tile's first barrier orders it before the first read)
   const int gw = __builtin_amdgcn_readfirstlane(tile * (WGD_THREADS / 64) + (int)(threadIdx.x >> 6));
   float* const outf = a.wpart + (size_t)split * DAD_H * DAD_D;
   const int GW = a.ntiles * (WGD_THREADS / 64);
   // CP = 3: the `_s16` sibling of the store variant, clean rows read from an fp16 / bf16 store in their
   // own type (block-uniform); a kernel of its own, so that the f32 kernels hold the f32 code alone
-  if constexpr (CP == 3) {
+  if constexpr (RG) {
+    // (CP = 2 here: the next batch, ragged too, is a store batch; its rows' type is block-uniform)
+    if constexpr (CP != 0) {
+      if (pc.xc_type() == DAD_STORE_F16)
+        wgd_tile<F16, CP, _Float16, true>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW, lps, lpz, rg_n);
+      else if (pc.xc_type() == DAD_STORE_BF16)
+        wgd_tile<F16, CP, __bf16, true>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW, lps, lpz, rg_n);
+      else
+        wgd_tile<F16, CP, float, true>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW, lps, lpz, rg_n);
+    } else {
+      wgd_tile<F16, 0, float, true>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW, lps, lpz, rg_n);
+    }
+  } else if constexpr (CP == 3) {
     if (pc.xc_type() == DAD_STORE_F16)
       wgd_tile<F16, 2, _Float16>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW);
     else
@@ -921,6 +1011,27 @@ __device__ __forceinline__ void wgrad_direct_body(const DadWgradArgs& a, const D
     wgd_tile<F16, CP>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW);
   }
 }
+
+#ifdef DAD_WGRAD_RG
+__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_rg(DadWgradArgs a, DadReduceArgs ra) {
+  DAD_GUARD_BLOCK(WGD_THREADS);
+  wgrad_direct_body<false, 0, true>(a, ra, DadPrepArgs{});
+}
+__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_f16_rg(DadWgradArgs a, DadReduceArgs ra) {
+  DAD_GUARD_BLOCK(WGD_THREADS);
+  wgrad_direct_body<true, 0, true>(a, ra, DadPrepArgs{});
+}
+__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_cps_rg(DadWgradArgs a, DadReduceArgs ra,
+                                                                         DadPrepArgs pc) {
+  DAD_GUARD_BLOCK(WGD_THREADS);
+  wgrad_direct_body<false, 2, true>(a, ra, pc);
+}
+__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_f16_cps_rg(DadWgradArgs a, DadReduceArgs ra,
+                                                                             DadPrepArgs pc) {
+  DAD_GUARD_BLOCK(WGD_THREADS);
+  wgrad_direct_body<true, 2, true>(a, ra, pc);
+}
+#else
 
 __global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct(DadWgradArgs a, DadReduceArgs ra) {
   DAD_GUARD_BLOCK(WGD_THREADS);
@@ -958,6 +1069,7 @@ __global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_f16_cps_s16(D
   DAD_GUARD_BLOCK(WGD_THREADS);
   wgrad_direct_body<true, 3>(a, ra, pc);
 }
+#endif   // DAD_WGRAD_RG
 
 // ---------------------------------------------------------------- reduce + squared norms
 // blocks [0, NB): DAD_REDUCE_COLS floats of dW1 each (+ squared-norm partial).
@@ -1056,10 +1168,11 @@ __device__ double extra_block_t(const DadReduceArgs& a, int e, int tid, float (*
   }
   return sq;
 }
-__device__ double extra_block(const DadReduceArgs& a, int e, int tid, float (*xs)[16][6]) {
+WGD_XLINK __device__ double extra_block(const DadReduceArgs& a, int e, int tid, float (*xs)[16][6]) {
   return a.keep1 ? extra_block_t<true>(a, e, tid, xs) : extra_block_t<false>(a, e, tid, xs);
 }
 
+#ifndef DAD_WGRAD_RG
 static_assert(DAD_REDUCE_THREADS == 4 * (DAD_REDUCE_COLS / 4), "dad_reduce: 4 split groups x float4 columns");
 static_assert(DAD_REDUCE_BLOCKS <= DAD_NORM_BLOCKS, "norm partials must fit the workspace");
 static_assert((DAD_NPARAM + 1023) / 1024 <= DAD_NORM_BLOCKS, "dad_norm partials must fit the workspace");
@@ -1151,3 +1264,4 @@ __global__ __launch_bounds__(256) void dad_norm(float* grad, float* normpart, fl
   __syncthreads();
   if (tid == 0) normpart[blockIdx.x] = (float)(((red[0] + red[1]) + red[2]) + red[3]);
 }
+#endif   // DAD_WGRAD_RG

@@ -19,13 +19,13 @@ from .step import DADStep
 
 
 class PretrainStep:
-    def __init__(self, model=None, lr=2e-4, weight_decay=1e-5, precision="fp32", device="cuda"):
+    def __init__(self, model=None, lr=2e-4, weight_decay=1e-5, precision="fp32", device="cuda", ragged=False):
         self.model = model if model is not None else SSRLModel().to(device)
         # IP/config.py:16-18 defaults; IP/train_for_clean.py:154-155 (Adam(L2), CrossEntropyLoss())
         self.view = ConfigView(flavor="iemocap", WARMUP_EPOCHS=1 << 30, USE_LABEL_SMOOTHING=False, DROPOUT_RATE=0.0,
                                GRADIENT_CLIPPING=False, LEARNING_RATE=lr, WEIGHT_DECAY=weight_decay,
                                LEARNING_RATE_SCHEDULER="none")
-        self.dad = DADStep(self.model, self.view, precision=precision, rng="counter")
+        self.dad = DADStep(self.model, self.view, precision=precision, rng="counter", ragged=ragged)
         self.lr = lr
 
     def step(self, batch, lr=None):

@@ -153,16 +153,28 @@ class DADStep:
             section 5): the side-stream layouts cost 21-40 us per step against the in-launch layout at
             windows of 0-20 us (the two cross-stream hops and the standalone preparation are exposed),
             so nothing is moved by default at any N; the option is for longer exchange windows.
+        ragged: FP16 / BF16 only (ValueError with 'fp32').  A step whose batches are all store batches
+            (data.StoreFeats read in place) then runs in ragged mode (dad_config.ragged): no launch reads,
+            computes or writes anything for a 32-frame slab that lies wholly past its utterance's end, so
+            the step's cost follows the frames that exist, not B x the longest utterance.  The lengths
+            are read on the device; the forward pass is bit-identical to the dense step's and the
+            gradient differs only by the summation order of the split partials (not at all when every
+            slab is live).  A step given a padded batch runs dense.  Off by default.
     """
 
     def __init__(self, model, cfg=None, flavor=None, precision="fp32", rng="counter", seed=0, comm=None,
-                 anchors=None, splits=0, prep_under_exchange=None):
+                 anchors=None, splits=0, prep_under_exchange=None, ragged=False):
         self.model = model
         self.view = cfg if isinstance(cfg, ConfigView) else ConfigView(cfg, flavor=flavor)
         self.device = model.student_flat.device
         if self.device.type != "cuda":
             raise RuntimeError("DADStep needs the model on an MI355X ('cuda') device")
         self.precision = PRECISIONS[precision]
+        self.ragged = bool(ragged)
+        if self.ragged:
+            if self.precision == _lib.PREC_FP32:
+                raise ValueError("ragged=True needs precision 'fp16' or 'bf16' (the FP32 step has no ragged mode)")
+            _lib.require("dad_step_ragged_plan", "ragged=True")     # (a build without the mode: rebuild)
         self.rng_mode = _lib.RNG_COUNTER if rng == "counter" else _lib.RNG_EXPLICIT
         self.seed = int(seed)
         self.comm = comm
@@ -314,7 +326,7 @@ class DADStep:
                                       splits=self.splits)
 
     _PREP_CFG = ("B", "T", "Bn", "Tn", "precision", "rng_mode", "seed", "counter", "warmup", "mask_len",
-                 "start_hi", "weak_std", "strong_std", "feat_p")
+                 "start_hi", "weak_std", "strong_std", "feat_p", "ragged")
     # (xc_dtype / xn_dtype follow from xc / xn: a store tensor has one dtype)
     _PREP_BT = ("xc", "mc", "xn", "mn", "nw", "ns", "u", "start", "rowc", "lenc", "rown", "lenn")
 
@@ -359,6 +371,8 @@ class DADStep:
             cfg.prepped = 0
         else:
             return None, None, None
+        # ragged mode: every batch of the step read in place from a store (the lengths are then on the device)
+        cfg.ragged = 1 if (self.ragged and rc is not None and (xn is None or rn is not None)) else 0
         bt = _lib.DadBatch()
         bt.xc, bt.mc, bt.yc = xc.data_ptr(), mc.data_ptr(), yc.data_ptr()
         if rc is not None:
