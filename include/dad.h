@@ -329,6 +329,42 @@ int dad_step_commit(const dad_config* cfg, const dad_state* st, void* workspace,
 
 /* DACPManager.update_class_quality_scores_epoch (I/utils.py:430-447) */
 int dad_epoch_end(const dad_config* cfg, const dad_state* st, void* stream);
+/* --- the confirmation-bias log, appended on the device (csrc/trace.hip) ----------------
+ * Replaces the logging loop of Trainer.train_step (I/train.py:425-437): for every row of the noisy batch whose
+ * sample id is tracked (Trainer.tracked_sample_indices, I/train.py:279-284) the reference appends
+ * {epoch, sample_id, pseudo_label, certainty_score, is_masked_in} to bias_analysis_log, reading the ids with
+ * .cpu() and three values per row with .item().  dad_trace_append appends the same entries, in the same order,
+ * to a device buffer, from what the step's tail launch left in its tail buffer; the host reads the buffer once,
+ * at the end of the run (I/train.py:691-700 writes it out).
+ *
+ * Trace buffer: int32 words, 16-byte aligned, zero-filled once by the caller; after that only dad_trace_append
+ * writes it.  Header, then `capacity` records.
+ *
+ * Added without an ABI bump (no existing structure or entry point changes): a library of ABI 10 built before
+ * them lacks the two symbols, and a binding reports that when a trace is asked for. */
+#define DAD_TRACE_HDR_WORDS 4      /* int32: [0] = records OFFERED so far (may exceed capacity; saturates at
+                                      2^31 - 1); [1..3] reserved, 0 */
+#define DAD_TRACE_REC_WORDS 4      /* int32 epoch | int32 sample_id | int32 label + flags | float certainty score */
+#define DAD_TRACE_MASKED_IN 0x100  /* flag in word 2: mask[i] != 0; the pseudo-label is word2 & 0xff */
+/* (DAD_TRACE_HDR_WORDS + capacity * DAD_TRACE_REC_WORDS) * 4; host only */
+size_t dad_trace_bytes(int64_t capacity);
+/* One step's entries.  tail: the step's tail buffer (dad_state.tail, DAD_TAIL_FLOATS(Bn)) after its tail launch
+ * was enqueued on `stream`: score = tail[DAD_TAIL_HDR + i], pred = tail[DAD_TAIL_HDR + Bn + i] (as float), mask =
+ * tail[DAD_TAIL_HDR + 2 Bn + i].  ids [Bn]: the noisy batch's sample ids (noisy_batch['id']).  tracked: a bitmap
+ * of ceil(n_samples / 32) words, bit (id & 31) of word (id >> 5) set = sample id is tracked.  Rows with
+ * 0 <= ids[i] < n_samples and their bit set are appended in batch order (ascending i) behind the records already
+ * there; rows with an id outside the range are ignored, and such an id never indexes the bitmap.  trace[0]
+ * counts every record offered; a record at a position >= capacity is dropped and nothing at or past word
+ * DAD_TRACE_HDR_WORDS + capacity * DAD_TRACE_REC_WORDS is written, so the host sees trace[0] > capacity and
+ * knows how many were lost.
+ * Enqueue-only like every entry point (no host read, no allocation, no synchronisation).  Two appends to one
+ * trace MUST be ordered on one stream (or by events): the cursor is read at the kernel's entry and written once
+ * at its exit, without atomics.
+ * DAD_E_ARG: a NULL pointer, or trace not 16-byte aligned; DAD_E_SHAPE: Bn outside [1, DAD_MAX_BATCH], n_samples
+ * outside [1, 2^31 - 1], capacity outside [0, 2^31 - 1]; all checked before anything is launched. */
+int dad_trace_append(const float* tail, int Bn, const int64_t* ids, const uint32_t* tracked, int64_t n_samples,
+                     int epoch, int32_t* trace, int64_t capacity, void* stream);
+
 /* refresh the 16-bit shadows of W1 after the caller changed student/teacher params
  * (e.g. load_complete_pretrained_weights, I/model.py:143-198): fp16 for precision
  * DAD_PREC_FP16, bf16 otherwise (the format the next step of that precision reads) */

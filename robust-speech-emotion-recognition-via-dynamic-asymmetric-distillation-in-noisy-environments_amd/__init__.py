@@ -16,10 +16,12 @@ from .step import DADStep
 from .dist import DPComm, ProcessGroupComm
 from .data import DeviceLoader, FeatureStore
 from .utils import DACPManager, DataAugmentation, ECDALoss
+from .trace import TrainingTrace
 from . import checkpoint, evaluate, pretrain
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
-           "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "build", "lib"]
+           "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "TrainingTrace",
+           "build", "lib"]
 
 
 def build(verbose=True):
@@ -32,5 +34,5 @@ def lib():
 
 
 _sys.modules.setdefault("dad_amd", _sys.modules[__name__])
-for _m in ("_build", "_lib", "config", "model", "step", "dist", "data", "utils", "evaluate", "checkpoint", "pretrain"):
+for _m in ("_build", "_lib", "config", "model", "step", "dist", "data", "utils", "evaluate", "checkpoint", "pretrain", "trace"):
     _sys.modules.setdefault("dad_amd." + _m, _sys.modules[__name__ + "." + _m])

@@ -29,6 +29,7 @@ T_TOTAL, T_CE, T_KL, T_ECDA, T_SCL, T_MSUM, T_CLIPNORM, T_CLIPCOEF = range(8)
 T_W, T_TAU_BEFORE, T_TAU_AFTER, T_FLOORED, T_ECDA_TERM, T_ECDA_GATE = 8, 12, 16, 20, 24, 28
 T_KL_ON, T_ECDA_ON, T_RANGE, T_TAU_HAT = 32, 33, 34, 40
 RANGE_NONFINITE, RANGE_POOL_TIMEOUT = 1, 2   # bits of the T_RANGE word (dad.h DAD_RANGE_*)
+TRACE_HDR_WORDS, TRACE_REC_WORDS, TRACE_MASKED_IN = 4, 4, 0x100   # dad.h DAD_TRACE_* (dad_trace_append)
 
 
 def tail_floats(bn):
@@ -180,6 +181,9 @@ EXPORTS = {
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "dad_rng_draws": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.c_int, ctypes.c_uint64, ctypes.c_size_t,
                                      ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_trace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "dad_trace_append": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "dad_timing_start": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "dad_timing_kernels": (ctypes.c_int, [ctypes.c_uint]),
     "dad_timing_reset": (ctypes.c_int, []),
@@ -195,7 +199,7 @@ EXPORTS = {
 
 # Entry points added without an ABI bump: a library of the same ABI version built before them loads, and
 # the feature that needs one reports the stale build when it is asked for (require()).
-OPTIONAL_EXPORTS = ("dad_step_ragged_plan",)
+OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_trace_bytes", "dad_trace_append")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

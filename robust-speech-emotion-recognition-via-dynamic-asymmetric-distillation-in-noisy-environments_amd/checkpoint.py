@@ -149,6 +149,8 @@ def train_epoch(step, clean_loader, noisy_loader, epoch, lr=None):
         tot = vec if tot is None else tot + vec
     if epoch >= step.view.WARMUP_EPOCHS:
         step.epoch_end()
+        if getattr(step, "trace", None) is not None:
+            step.trace.end_epoch(step)      # the epoch's DACP / ECDA history rows (I/train.py:498-517), on the device
     if tot is None:
         return {}
     # the range flag (dad.h DAD_T_RANGE, every batch shape's word) rides in the epoch's one

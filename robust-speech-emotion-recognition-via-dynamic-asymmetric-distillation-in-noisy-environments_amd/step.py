@@ -160,10 +160,16 @@ class DADStep:
             are read on the device; the forward pass is bit-identical to the dense step's and the
             gradient differs only by the summation order of the split partials (not at all when every
             slab is live).  A step given a padded batch runs dense.  Off by default.
+        trace: optional `trace.TrainingTrace` (also settable later: `step.trace = tr`).  Every post-warm-up
+            step whose noisy batch dict has an 'id' (the reference's `'id' in noisy_batch`, I/train.py:425;
+            CASIA / EMODB batches carry none) then enqueues one dad_trace_append behind its tail launch: the
+            confirmation-bias log entries of the batch's tracked samples, appended on the device.  A step
+            whose update is skipped (non-finite loss) is logged too: the reference logs before the loss
+            exists.  Without a trace nothing is launched or allocated and no result differs.
     """
 
     def __init__(self, model, cfg=None, flavor=None, precision="fp32", rng="counter", seed=0, comm=None,
-                 anchors=None, splits=0, prep_under_exchange=None, ragged=False):
+                 anchors=None, splits=0, prep_under_exchange=None, ragged=False, trace=None):
         self.model = model
         self.view = cfg if isinstance(cfg, ConfigView) else ConfigView(cfg, flavor=flavor)
         self.device = model.student_flat.device
@@ -206,6 +212,7 @@ class DADStep:
         self.prep_under_exchange = 0 if prep_under_exchange is None else prep_under_exchange
         self._side = None            # the side stream of the preparation under the exchange
         self._prep_event = None      # recorded after it: the next step's encoder waits for it
+        self.trace = trace
         self.refresh_shadow()
 
     # ----------------------------------------------------------------------------- state
@@ -439,6 +446,7 @@ class DADStep:
         if self._shadow_dirty or self._param_key() != self._shadow_key:
             self.refresh_shadow()
         cfg, bt, st = self._prepare(clean_batch, noisy_batch, epoch, lr, draws)
+        trace_ids = None if self.trace is None else self._trace_ids(cfg, noisy_batch)
         pk, self._prepped_key = self._prepped_key, None
         cfg.prepped = 1 if (pk is not None and pk == self._prep_key(cfg, bt)) else 0
         self.last_prepped = bool(cfg.prepped)   # diagnostics: this step's rows came from the last tail launch
@@ -474,6 +482,8 @@ class DADStep:
         else:
             _lib.check(L.dad_step_backward(cfg, bt, st, _lib.ptr(ws), stream), "dad_step_backward")
         self._ahead = (done, pending)
+        if trace_ids is not None:       # behind the tail launch, which the backward just enqueued
+            self.trace.append(self._last["tail"], cfg.Bn, trace_ids, epoch, stream)
         if pending.value:
             # the next batch's remaining rows on the side stream, from the end of the backward on:
             # under the all-reduce (and the optimizer), on CUs the exchange leaves idle
@@ -497,6 +507,15 @@ class DADStep:
         self.adam_step += 1
         self.global_step += 1
         return self.losses()
+
+    def _trace_ids(self, cfg, noisy_batch):
+        """The sample ids this step logs into the attached trace (I/train.py:425: tracking is on and
+        `'id' in noisy_batch`; the branch lies past the warm-up return, I/train.py:402), on the device, or None.
+        Checked before anything is enqueued: an 'id' that does not match the batch is a ValueError."""
+        tr = self.trace
+        if cfg.warmup or noisy_batch is None or not tr.active or noisy_batch.get("id") is None:
+            return None
+        return tr.device_ids(noisy_batch["id"], cfg.Bn)
 
     def _defer_parts(self):
         """prep_under_exchange as a DAD_PREP_* mask (True: the clean rows)."""
@@ -527,10 +546,13 @@ class DADStep:
         self._join_side()
         self._prepped_key = None     # (this step prepares its own rows into the workspace)
         cfg, bt, st = self._prepare(clean_batch, noisy_batch, epoch, None, draws)
+        trace_ids = None if self.trace is None else self._trace_ids(cfg, noisy_batch)
         ws = self._workspace(cfg)
         stream = self._stream()
         L = _lib.lib()
         _lib.check(L.dad_step_compute(cfg, bt, st, _lib.ptr(ws), stream), "dad_step_compute")
+        if trace_ids is not None:
+            self.trace.append(self._last["tail"], cfg.Bn, trace_ids, epoch, stream)
         _lib.check(L.dad_step_commit(cfg, st, _lib.ptr(ws), stream), "dad_step_commit")
         self.global_step += 1
         self._shadow_dirty = True
