@@ -496,6 +496,50 @@ size_t dad_eval_workspace_bytes(int64_t n, int64_t slabs, int precision, int wit
  * slabs outside [0, n * 2^26]; DAD_E_UNSUPPORTED: DAD_PREC_BF16. */
 int dad_eval_split(const dad_eval_args* args, void* workspace, void* stream);
 
+/* --- class separation of a split's embeddings (csrc/cluster.hip) -------------------------
+ * calculate_cluster_metrics (I/iemocap_plot_tsne.py:390-398): scikit-learn's silhouette_score and
+ * calinski_harabasz_score of emb [n][256] (dad_eval_split's emb / t_emb) under labels [n], whose
+ * values generate_analysis_report (I/iemocap_plot_tsne.py:400-470) writes into `cluster_analysis`.
+ * Only rows with a label in [0, 4) take part (m of them, k classes present, n_c per class).  With
+ * d(i, j) the Euclidean distance (d(i, i) = 0): a(i) = sum of d(i, j) over the other rows of i's class
+ * / (n_c - 1); b(i) = min over the other present classes of the mean d(i, j) to their rows;
+ * s(i) = (b - a) / max(a, b), 0 when n_c = 1 or max(a, b) = 0; silhouette = mean s(i).
+ * CH = (B / (k - 1)) / (W / (m - k)), B = sum_c n_c |mu_c - mu|^2, W = sum_i |x_i - mu_{y_i}|^2, 1.0 when
+ * W = 0.  Both are defined for 2 <= k <= m - 1 only; otherwise (scikit-learn raises, the reference
+ * reports (0.0, 0.0)) DAD_CM_VALID is 0, both scores are 0.0 and every s(i) is 0.
+ * The distances come from a Gram pass on the fp32 matrix cores, d = sqrt(max(|x_i|^2 + |x_j|^2 - 2 x_i.x_j,
+ * 0)) on rows centred on the labelled rows' mean (a shift changes no distance and removes the common
+ * post-ReLU offset from the cancellation); the per-row class sums are added in a fixed order (no floating-point atomics), so two calls on
+ * the same inputs write bit-identical outputs.  Rows past n are never read.
+ * out [DAD_CM_SLOTS] doubles (device); sil [n] (device, may be NULL) receives s(i), 0 for an unlabelled row. */
+#define DAD_CM_SILHOUETTE 0
+#define DAD_CM_CH 1
+#define DAD_CM_VALID 2          /* 1.0 / 0.0 */
+#define DAD_CM_M 3              /* labelled rows */
+#define DAD_CM_K 4              /* classes present */
+#define DAD_CM_COUNTS 5         /* [4] n_c */
+#define DAD_CM_SIL_CLASS 9      /* [4] mean s(i) of the class (0 for an absent class) */
+#define DAD_CM_W 13
+#define DAD_CM_B 14
+#define DAD_CM_NONFINITE 15     /* labelled rows with a non-finite component (the scores are then meaningless) */
+#define DAD_CM_SLOTS 16
+#define DAD_CM_MAX_N 65536      /* largest n */
+#define DAD_CM_TILE 64          /* rows / columns of a tile of the pairwise pass */
+#define DAD_CM_MAX_CHUNKS 16    /* most column chunks a row tile is split into */
+/* workspace bytes of dad_cluster_metrics (0 for an unsupported n); no initialisation needed */
+size_t dad_cluster_workspace_bytes(int64_t n);
+/* DAD_E_ARG: emb, labels, out or workspace is NULL; DAD_E_SHAPE: n < 1 or n > DAD_CM_MAX_N. */
+int dad_cluster_metrics(const float* emb, const int64_t* labels, int64_t n, double* out, float* sil,
+                        void* workspace, void* stream);
+/* The grid of the pairwise pass for n rows on a device of `cus` compute units: ceil(n / 64) row tiles,
+ * each split into `chunks` runs of tiles_per_chunk column tiles (the last may be shorter, none is
+ * empty), chunks <= min(row tiles, DAD_CM_MAX_CHUNKS).  Host only. */
+int dad_cluster_plan(int64_t n, int cus, int* row_tiles, int* chunks, int* tiles_per_chunk);
+/* dad_cluster_metrics with the chunk count asked for (clamped as dad_cluster_plan clamps it; <= 0: the
+ * plan's), for tests of the chunked summation at small n. */
+int dad_cluster_metrics_chunked(const float* emb, const int64_t* labels, int64_t n, double* out, float* sil,
+                                int chunks, void* workspace, void* stream);
+
 /* --- the reference's helper types as operators (I/utils.py:317-652) -------------------
  * For trainer code that drives DataAugmentation / DACPManager / ECDALoss itself (the
  * train_step shim's callers, anchor calibration, I/train.py:334,341).  Same device functions

@@ -18,10 +18,11 @@ from .data import DeviceLoader, FeatureStore
 from .utils import DACPManager, DataAugmentation, ECDALoss
 from .trace import TrainingTrace
 from . import checkpoint, evaluate, pretrain
+from .evaluate import cluster_metrics, cluster_metrics_store, separation_report
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
            "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "TrainingTrace",
-           "build", "lib"]
+           "cluster_metrics", "cluster_metrics_store", "separation_report", "build", "lib"]
 
 
 def build(verbose=True):

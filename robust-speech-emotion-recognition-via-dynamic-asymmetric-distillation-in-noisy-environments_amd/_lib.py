@@ -31,6 +31,10 @@ T_KL_ON, T_ECDA_ON, T_RANGE, T_TAU_HAT = 32, 33, 34, 40
 RANGE_NONFINITE, RANGE_POOL_TIMEOUT = 1, 2   # bits of the T_RANGE word (dad.h DAD_RANGE_*)
 TRACE_HDR_WORDS, TRACE_REC_WORDS, TRACE_MASKED_IN = 4, 4, 0x100   # dad.h DAD_TRACE_* (dad_trace_append)
 
+# result block of dad_cluster_metrics (dad.h DAD_CM_*): float64 slots
+CM_SILHOUETTE, CM_CH, CM_VALID, CM_M, CM_K, CM_COUNTS, CM_SIL_CLASS, CM_W, CM_B, CM_NONFINITE = 0, 1, 2, 3, 4, 5, 9, 13, 14, 15
+CM_SLOTS, CM_MAX_N, CM_TILE, CM_MAX_CHUNKS = 16, 65536, 64, 16
+
 
 def tail_floats(bn):
     return DAD_TAIL_HDR + bn * 7
@@ -184,6 +188,13 @@ EXPORTS = {
     "dad_trace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "dad_trace_append": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                         ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "dad_cluster_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "dad_cluster_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_cluster_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "dad_cluster_metrics_chunked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "dad_timing_start": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "dad_timing_kernels": (ctypes.c_int, [ctypes.c_uint]),
     "dad_timing_reset": (ctypes.c_int, []),
@@ -199,7 +210,9 @@ EXPORTS = {
 
 # Entry points added without an ABI bump: a library of the same ABI version built before them loads, and
 # the feature that needs one reports the stale build when it is asked for (require()).
-OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_trace_bytes", "dad_trace_append")
+OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_trace_bytes", "dad_trace_append",
+                    "dad_cluster_workspace_bytes", "dad_cluster_metrics", "dad_cluster_plan",
+                    "dad_cluster_metrics_chunked")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

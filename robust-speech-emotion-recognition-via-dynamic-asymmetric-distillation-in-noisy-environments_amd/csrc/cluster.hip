@@ -1,0 +1,483 @@
+// Class separation of a split's embeddings on the device: silhouette and Calinski-Harabasz.
+//
+// Replaces calculate_cluster_metrics (I/iemocap_plot_tsne.py:390-398): scikit-learn's silhouette_score
+// and calinski_harabasz_score on the [n][256] embeddings of a split, with scikit-learn's meaning
+// (include/dad.h restates it).  Six launches, no floating-point atomics, every sum in a fixed order:
+//
+//   dad_cluster_prep   one workgroup per 64-row tile: the tile's per-class column sums in double, its class
+//                      counts and its count of labelled rows with a non-finite component
+//   dad_cluster_stats  one workgroup: class sums over the tiles in tile order -> counts, m, k, the valid
+//                      flag, the centroids (double), B, and the labelled rows' mean mu rounded to fp32
+//   dad_cluster_norms  |x_i - mu|^2 per row, as the diagonal of the pair kernel's own Gram block.
+//                      Distances do not change under a shift, and post-ReLU embeddings share a large positive
+//                      mean: with every operand centred on mu the identity |a|^2 + |b|^2 - 2 a.b cancels
+//                      numbers of the size of the spread, not of the mean (|x|^2 ~ 90 against |x - mu|^2 ~ 3
+//                      on the tests' inputs).  Both kernels subtract the same fp32 mu from the same fp32 x.
+//   dad_cluster_pair   the n x n pass.  Workgroup (row tile, chunk) owns 64 rows and a contiguous run of
+//                      64-column tiles.  Each of its 4 waves holds 32 rows of the row tile in registers as
+//                      the A operand of v_mfma_f32_32x32x2_f32 (lane = row, 4 consecutive k per k-block of
+//                      8 and lane half) and owns one 32 x 32 quadrant of every 64 x 64 tile; the column
+//                      tile's rows are staged through LDS (row stride 260 floats: the 16-byte operand reads
+//                      of 8 consecutive rows cover the 32 banks once), with the columns' norms and labels.
+//                      The epilogue turns the Gram block into distances, zeroes the diagonal, and adds each
+//                      distance to the bin of its column's class, per lane; unlabelled and padding columns
+//                      match no bin.  After the last tile the bins cross the 32 lanes of a row by a fixed
+//                      xor tree, the two column halves meet in LDS, and the workgroup writes its [64][4]
+//                      sums to the workspace.  The distance matrix never exists in memory.
+//   dad_cluster_rows   one workgroup per row tile: adds the chunks in chunk order, forms a, b, s per row,
+//                      |x_i - mu_c|^2 in double, and the tile's sums of s per class and of W
+//   dad_cluster_final  one workgroup: the tiles in tile order -> the result block
+//
+// Work per call (rt = ceil(n / 64) row tiles): the pair kernel runs 2 * 256 * (64 rt)^2 FLOP on the fp32 matrix
+// cores and stages rt * rt column tiles of 64 KB plus rt * chunks row tiles from L2 (the embeddings are 1 KB a
+// row); the other launches read the embeddings three more times.  DESIGN.md 6b has the measured figures.
+#include <cstdint>
+
+#include "dad_common.h"
+
+int device_cus(int* out);   // dad_abi.hip
+
+namespace {
+
+constexpr int kTile = DAD_CM_TILE;         // rows and columns of a tile
+constexpr int kLd = DAD_H + 4;             // LDS row stride of the column tile, floats
+constexpr int kThreads = 256;
+constexpr int kMaxChunks = DAD_CM_MAX_CHUNKS;
+
+static_assert(kTile == 64 && DAD_H == 256 && DAD_C == 4, "the pair kernel's wave / lane mapping");
+
+struct ClusterWs {
+  size_t norms, part, csum, cnt, cent, mean, hdr_i, hdr_d, wpart, silpart, bytes;
+};
+
+// (a function of n alone: the chunk count a call runs with is at most min(column tiles, kMaxChunks))
+ClusterWs cluster_ws_layout(int64_t n) {
+  ClusterWs w;
+  const size_t rt = (size_t)((n + kTile - 1) / kTile), npad = rt * kTile;
+  const size_t maxc = rt < (size_t)kMaxChunks ? rt : (size_t)kMaxChunks;
+  size_t off = 0;
+  w.norms = off;   off = dad_align(off + sizeof(float) * npad);
+  w.part = off;    off = dad_align(off + sizeof(float) * maxc * npad * DAD_C);
+  w.csum = off;    off = dad_align(off + sizeof(double) * rt * DAD_C * DAD_H);
+  w.cnt = off;     off = dad_align(off + sizeof(int32_t) * rt * 8);
+  w.cent = off;    off = dad_align(off + sizeof(double) * DAD_C * DAD_H);
+  w.mean = off;    off = dad_align(off + sizeof(float) * DAD_H);
+  w.hdr_i = off;   off = dad_align(off + sizeof(int32_t) * 8);
+  w.hdr_d = off;   off = dad_align(off + sizeof(double) * 2);
+  w.wpart = off;   off = dad_align(off + sizeof(double) * rt);
+  w.silpart = off; off = dad_align(off + sizeof(double) * rt * DAD_C);
+  w.bytes = off;
+  return w;
+}
+
+// hdr_i slots
+constexpr int kHN0 = 0, kHM = 4, kHK = 5, kHValid = 6, kHBad = 7;
+
+__device__ __forceinline__ int class_of(long lab) { return lab >= 0 && lab < DAD_C ? (int)lab : -1; }
+__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+}  // namespace
+
+__global__ __launch_bounds__(kThreads) void dad_cluster_prep(const float* __restrict__ emb,
+                                                             const int64_t* __restrict__ labels, int n,
+                                                             double* __restrict__ csum, int32_t* __restrict__ cnt) {
+  __shared__ int lab_s[kTile], bad_s[kTile];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = blockIdx.x, i0 = kTile * tile;
+  if (tid < kTile) lab_s[tid] = i0 + tid < n ? class_of(labels[i0 + tid]) : -1;
+  __syncthreads();
+  for (int rr = w; rr < kTile; rr += kThreads / 64) {
+    const int i = i0 + rr;           // (uniform in the wave)
+    bool bad = false;
+    if (i < n) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(emb + (size_t)i * DAD_H + 4 * lane);
+      bad = __ballot(nonfinite(v[0]) | nonfinite(v[1]) | nonfinite(v[2]) | nonfinite(v[3])) != 0ull;
+    }
+    if (lane == 0) bad_s[rr] = bad && lab_s[rr] >= 0;
+  }
+  double s[DAD_C] = {0.0, 0.0, 0.0, 0.0};
+  const int rows = n - i0 < kTile ? n - i0 : kTile;
+  for (int rr = 0; rr < rows; ++rr) {
+    const int c = lab_s[rr];
+    if (c < 0) continue;             // (an unlabelled row is not read: its NaNs stay out)
+    const double x = (double)emb[(size_t)(i0 + rr) * DAD_H + tid];
+#pragma unroll
+    for (int k = 0; k < DAD_C; ++k) s[k] += c == k ? x : 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < DAD_C; ++k) csum[((size_t)tile * DAD_C + k) * DAD_H + tid] = s[k];
+  __syncthreads();
+  if (tid < 8) {
+    int v = 0;
+    if (tid < DAD_C) for (int rr = 0; rr < kTile; ++rr) v += lab_s[rr] == tid;
+    else if (tid == 4) for (int rr = 0; rr < kTile; ++rr) v += bad_s[rr];
+    cnt[tile * 8 + tid] = v;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void dad_cluster_stats(const double* __restrict__ csum,
+                                                              const int32_t* __restrict__ cnt, int rt,
+                                                              double* __restrict__ cent, float* __restrict__ mean,
+                                                              int32_t* __restrict__ hdr_i,
+                                                              double* __restrict__ hdr_d) {
+  __shared__ double red[kThreads];
+  const int tid = threadIdx.x;
+  double s[DAD_C] = {0.0, 0.0, 0.0, 0.0};
+  int nc[DAD_C] = {0, 0, 0, 0}, bad = 0;
+  for (int t = 0; t < rt; ++t) {
+#pragma unroll
+    for (int k = 0; k < DAD_C; ++k) {
+      s[k] += csum[((size_t)t * DAD_C + k) * DAD_H + tid];
+      nc[k] += cnt[t * 8 + k];
+    }
+    bad += cnt[t * 8 + 4];
+  }
+  const int m = nc[0] + nc[1] + nc[2] + nc[3];
+  const int k = (nc[0] > 0) + (nc[1] > 0) + (nc[2] > 0) + (nc[3] > 0);
+  const double mu = m > 0 ? (((s[0] + s[1]) + s[2]) + s[3]) / (double)m : 0.0;
+  mean[tid] = (float)mu;
+  double b = 0.0;
+#pragma unroll
+  for (int c = 0; c < DAD_C; ++c) {
+    const double mc = nc[c] > 0 ? s[c] / (double)nc[c] : 0.0;
+    cent[c * DAD_H + tid] = mc;
+    b += nc[c] > 0 ? (double)nc[c] * ((mc - mu) * (mc - mu)) : 0.0;
+  }
+  red[tid] = b;
+  __syncthreads();
+  if (tid == 0) {
+    double bs = 0.0;
+    for (int d = 0; d < kThreads; ++d) bs += red[d];
+#pragma unroll
+    for (int c = 0; c < DAD_C; ++c) hdr_i[kHN0 + c] = nc[c];
+    hdr_i[kHM] = m;
+    hdr_i[kHK] = k;
+    hdr_i[kHValid] = k >= 2 && k <= m - 1;
+    hdr_i[kHBad] = bad;
+    hdr_d[0] = bs;
+  }
+}
+
+// |x_i - mu|^2 as the diagonal of the pair kernel's own Gram block: the same operand values through the same
+// chain of 128 MFMAs, so (x_i - mu).(x_j - mu) of an exact duplicate j equals it bit for bit and their distance
+// is exactly 0.  One wave per 32 rows.
+__global__ __launch_bounds__(128) void dad_cluster_norms(const float* __restrict__ emb,
+                                                         const float* __restrict__ mean, int n,
+                                                         float* __restrict__ norms) {
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int kh = lane >> 5, l32 = lane & 31;
+  const int r0 = kTile * (int)blockIdx.x + 32 * w, ia = r0 + l32;
+  const float* ra = emb + (size_t)(ia < n ? ia : 0) * DAD_H + 4 * kh;
+  f32x16 acc = f32x16{};
+#pragma unroll 4
+  for (int q = 0; q < DAD_H / 8; ++q) {
+    const f32x4 v = ia < n ? *reinterpret_cast<const f32x4*>(ra + 8 * q) -
+                                 *reinterpret_cast<const f32x4*>(mean + 4 * kh + 8 * q)
+                           : f32x4{};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(v[e], v[e], acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (l32 == dad_acc_row(r, kh)) norms[r0 + l32] = acc[r];   // (rt * 64 entries: padding rows get 0)
+}
+
+struct ClusterPairArgs {
+  const float* emb;
+  const int64_t* labels;
+  const float* norms;
+  const float* mean;
+  float* part;      // [chunks][npad][4]
+  int n, npad, ct, per;
+};
+
+// (two workgroups per CU, so one stages its next column tile while the other multiplies: 256 registers a lane)
+__global__ __launch_bounds__(kThreads, 2) void dad_cluster_pair(ClusterPairArgs a) {
+  __shared__ __attribute__((aligned(16))) float bt[kTile * kLd];
+  __shared__ float nj_s[kTile], ni_s[kTile];
+  __shared__ int lj_s[kTile];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kh = lane >> 5, l32 = lane & 31;
+  const int rh = w >> 1, ch = w & 1;
+  const int n = a.n;
+  const int i0 = kTile * (int)blockIdx.x, chunk = blockIdx.y;
+
+  // A operand: row i0 + 32 rh + l32; MFMA step e of k-block q takes k = 8 q + 4 kh + e on both operands
+  f32x4 av[DAD_H / 8];
+  {
+    const int ia = i0 + 32 * rh + l32;
+    const float* ra = a.emb + (size_t)(ia < n ? ia : 0) * DAD_H + 4 * kh;
+#pragma unroll
+    for (int q = 0; q < DAD_H / 8; ++q)
+      av[q] = ia < n ? *reinterpret_cast<const f32x4*>(ra + 8 * q) -
+                           *reinterpret_cast<const f32x4*>(a.mean + 4 * kh + 8 * q)
+                     : f32x4{};
+  }
+  const f32x4 mu4 = *reinterpret_cast<const f32x4*>(a.mean + 4 * (tid & 63));   // the columns this thread stages
+  if (tid < kTile) ni_s[tid] = a.norms[i0 + tid];
+  float bins[16][DAD_C];
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+#pragma unroll
+    for (int c = 0; c < DAD_C; ++c) bins[r][c] = 0.0f;
+
+  const int t_end = (chunk + 1) * a.per < a.ct ? (chunk + 1) * a.per : a.ct;
+  for (int t = chunk * a.per; t < t_end; ++t) {
+    const int j0 = kTile * t;
+    __syncthreads();      // the previous tile's operand reads are done
+#pragma unroll
+    for (int e = 0; e < kTile * (DAD_H / 4) / kThreads; ++e) {
+      const int idx = tid + kThreads * e, r = idx >> 6, c4 = 4 * (idx & 63), j = j0 + r;   // (idx & 63 = tid & 63)
+      const f32x4 v = j < n ? *reinterpret_cast<const f32x4*>(a.emb + (size_t)j * DAD_H + c4) - mu4 : f32x4{};
+      *reinterpret_cast<f32x4*>(&bt[r * kLd + c4]) = v;
+    }
+    if (tid < kTile) {
+      const int j = j0 + tid;
+      nj_s[tid] = j < n ? a.norms[j] : 0.0f;
+      lj_s[tid] = j < n ? class_of(a.labels[j]) : -1;
+    }
+    __syncthreads();
+    const int jc = 32 * ch + l32;
+    const float* rb = &bt[jc * kLd + 4 * kh];
+    f32x16 acc = f32x16{};
+#pragma unroll
+    for (int q = 0; q < DAD_H / 8; ++q) {
+      const f32x4 bv = *reinterpret_cast<const f32x4*>(rb + 8 * q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q][e], bv[e], acc, 0, 0, 0);
+    }
+    const int cj = lj_s[jc], jg = j0 + jc;
+    const float nj = nj_s[jc];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int il = 32 * rh + dad_acc_row(r, kh);
+      float d = sqrtf(fmaxf((ni_s[il] + nj) - 2.0f * acc[r], 0.0f));
+      d = i0 + il == jg ? 0.0f : d;
+#pragma unroll
+      for (int c = 0; c < DAD_C; ++c) bins[r][c] += cj == c ? d : 0.0f;
+    }
+  }
+  // the 32 columns of a lane half -> lane l32 = 0, by a fixed tree
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+#pragma unroll
+    for (int c = 0; c < DAD_C; ++c) {
+      float v = bins[r][c];
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      bins[r][c] = v;
+    }
+  __syncthreads();        // the last tile's operand reads are done: bt becomes red[2][64][4]
+  if (l32 == 0) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int il = 32 * rh + dad_acc_row(r, kh);
+      *reinterpret_cast<f32x4*>(&bt[(ch * kTile + il) * DAD_C]) = f32x4{bins[r][0], bins[r][1], bins[r][2], bins[r][3]};
+    }
+  }
+  __syncthreads();
+  a.part[((size_t)chunk * a.npad + i0) * DAD_C + tid] = bt[tid] + bt[kTile * DAD_C + tid];
+}
+
+struct ClusterRowArgs {
+  const float* emb;
+  const int64_t* labels;
+  const float* part;
+  const double* cent;
+  const int32_t* hdr_i;
+  float* sil;        // [n] or NULL
+  double* wpart;     // [rt]
+  double* silpart;   // [rt][4]
+  int n, npad, chunks;
+};
+
+__global__ __launch_bounds__(kThreads) void dad_cluster_rows(ClusterRowArgs a) {
+  __shared__ int lab_s[kTile];
+  __shared__ double w_s[kTile], s_s[kTile];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = blockIdx.x, i0 = kTile * tile, n = a.n;
+  if (tid < kTile) {
+    const int i = i0 + tid;
+    const int c = i < n ? class_of(a.labels[i]) : -1;
+    lab_s[tid] = c;
+    double s = 0.0;
+    if (c >= 0 && a.hdr_i[kHValid]) {
+      float sum[DAD_C] = {0.0f, 0.0f, 0.0f, 0.0f};
+      for (int q = 0; q < a.chunks; ++q) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(a.part + ((size_t)q * a.npad + i) * DAD_C);
+#pragma unroll
+        for (int k = 0; k < DAD_C; ++k) sum[k] += v[k];
+      }
+      double own = 0.0, other = 0.0;
+      int nown = 0;
+      bool have = false;
+#pragma unroll
+      for (int k = 0; k < DAD_C; ++k) {
+        const int nk = a.hdr_i[kHN0 + k];
+        if (k == c) {
+          own = (double)sum[k];
+          nown = nk;
+        } else if (nk > 0) {
+          const double mean = (double)sum[k] / (double)nk;
+          other = have ? (mean < other ? mean : other) : mean;
+          have = true;
+        }
+      }
+      if (nown > 1 && have) {
+        const double av = own / (double)(nown - 1);
+        const double mx = av > other ? av : other;
+        s = mx > 0.0 ? (other - av) / mx : 0.0;
+      }
+    }
+    s_s[tid] = s;
+    if (a.sil && i < n) a.sil[i] = (float)s;
+  }
+  __syncthreads();
+  for (int rr = w; rr < kTile; rr += kThreads / 64) {
+    const int c = lab_s[rr];         // (uniform in the wave)
+    double ws = 0.0;
+    if (c >= 0) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(a.emb + (size_t)(i0 + rr) * DAD_H + 4 * lane);
+      const double* mu = a.cent + c * DAD_H + 4 * lane;
+      double p = 0.0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double d = (double)v[e] - mu[e];
+        p += d * d;
+      }
+      ws = dad_wave_sum_d(p);
+    }
+    if (lane == 0) w_s[rr] = ws;
+  }
+  __syncthreads();
+  if (tid < DAD_C) {
+    double s = 0.0;
+    for (int rr = 0; rr < kTile; ++rr) s += lab_s[rr] == tid ? s_s[rr] : 0.0;
+    a.silpart[tile * DAD_C + tid] = s;
+  } else if (tid == DAD_C) {
+    double s = 0.0;
+    for (int rr = 0; rr < kTile; ++rr) s += w_s[rr];
+    a.wpart[tile] = s;
+  }
+}
+
+__global__ __launch_bounds__(64) void dad_cluster_final(const double* __restrict__ wpart,
+                                                        const double* __restrict__ silpart,
+                                                        const int32_t* __restrict__ hdr_i,
+                                                        const double* __restrict__ hdr_d, int rt,
+                                                        double* __restrict__ out) {
+  __shared__ double v_s[DAD_C + 1];
+  const int tid = threadIdx.x;
+  if (tid <= DAD_C) {
+    double s = 0.0;
+    if (tid < DAD_C) for (int t = 0; t < rt; ++t) s += silpart[t * DAD_C + tid];
+    else for (int t = 0; t < rt; ++t) s += wpart[t];
+    v_s[tid] = s;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int m = hdr_i[kHM], k = hdr_i[kHK];
+    const bool valid = hdr_i[kHValid] != 0;
+    const double W = v_s[DAD_C], B = hdr_d[0];
+    const double stot = ((v_s[0] + v_s[1]) + v_s[2]) + v_s[3];
+    out[DAD_CM_SILHOUETTE] = valid ? stot / (double)m : 0.0;
+    out[DAD_CM_CH] = !valid ? 0.0 : (W == 0.0 ? 1.0 : (B * (double)(m - k)) / (W * ((double)k - 1.0)));
+    out[DAD_CM_VALID] = valid ? 1.0 : 0.0;
+    out[DAD_CM_M] = (double)m;
+    out[DAD_CM_K] = (double)k;
+    for (int c = 0; c < DAD_C; ++c) {
+      const int nc = hdr_i[kHN0 + c];
+      out[DAD_CM_COUNTS + c] = (double)nc;
+      out[DAD_CM_SIL_CLASS + c] = valid && nc > 0 ? v_s[c] / (double)nc : 0.0;
+    }
+    out[DAD_CM_W] = W;
+    out[DAD_CM_B] = B;
+    out[DAD_CM_NONFINITE] = (double)hdr_i[kHBad];
+  }
+}
+
+#define CM_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
+
+extern "C" int dad_cluster_plan(int64_t n, int cus, int* row_tiles, int* chunks, int* tiles_per_chunk) {
+  if (!row_tiles || !chunks || !tiles_per_chunk) return DAD_E_ARG;
+  if (n < 1 || n > DAD_CM_MAX_N || cus < 1) return DAD_E_SHAPE;
+  // two workgroups of the pair kernel fit a CU (65 KB of LDS each): the most chunks whose grid is still
+  // resident at once (rounding up instead left 5,531 rows on 256 CUs a second round of 10 workgroups as
+  // long as the first of 512)
+  const int rt = (int)((n + kTile - 1) / kTile);
+  int want = 2 * cus / rt;
+  const int cap = rt < kMaxChunks ? rt : kMaxChunks;
+  want = want < 1 ? 1 : (want > cap ? cap : want);
+  const int per = (rt + want - 1) / want;
+  *row_tiles = rt;
+  *tiles_per_chunk = per;
+  *chunks = (rt + per - 1) / per;        // (no empty chunk)
+  return DAD_OK;
+}
+
+extern "C" size_t dad_cluster_workspace_bytes(int64_t n) {
+  if (n < 1 || n > DAD_CM_MAX_N) return 0;
+  return cluster_ws_layout(n).bytes;
+}
+
+extern "C" int dad_cluster_metrics_chunked(const float* emb, const int64_t* labels, int64_t n, double* out, float* sil,
+                                           int chunks, void* workspace, void* stream_) {
+  if (!emb || !labels || !out || !workspace) return DAD_E_ARG;
+  if (n < 1 || n > DAD_CM_MAX_N) return DAD_E_SHAPE;
+  int rt = 0, nch = 0, per = 0;
+  if (chunks <= 0) {
+    int cus = 0;
+    const int rc = device_cus(&cus);
+    if (rc) return rc;
+    const int pr = dad_cluster_plan(n, cus, &rt, &nch, &per);
+    if (pr) return pr;
+  } else {
+    rt = (int)((n + kTile - 1) / kTile);
+    const int cap = rt < kMaxChunks ? rt : kMaxChunks;
+    const int want = chunks > cap ? cap : chunks;
+    per = (rt + want - 1) / want;
+    nch = (rt + per - 1) / per;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  const ClusterWs L = cluster_ws_layout(n);
+  char* ws = (char*)workspace;
+  float* norms = (float*)(ws + L.norms);
+  float* part = (float*)(ws + L.part);
+  double* csum = (double*)(ws + L.csum);
+  int32_t* cnt = (int32_t*)(ws + L.cnt);
+  double* cent = (double*)(ws + L.cent);
+  float* mean = (float*)(ws + L.mean);
+  int32_t* hdr_i = (int32_t*)(ws + L.hdr_i);
+  double* hdr_d = (double*)(ws + L.hdr_d);
+  double* wpart = (double*)(ws + L.wpart);
+  double* silpart = (double*)(ws + L.silpart);
+
+  hipLaunchKernelGGL(dad_cluster_prep, dim3(rt), dim3(kThreads), 0, stream, emb, labels, (int)n, csum, cnt);
+  CM_TRY(hipGetLastError());
+  hipLaunchKernelGGL(dad_cluster_stats, dim3(1), dim3(kThreads), 0, stream, csum, cnt, rt, cent, mean, hdr_i, hdr_d);
+  CM_TRY(hipGetLastError());
+  hipLaunchKernelGGL(dad_cluster_norms, dim3(rt), dim3(128), 0, stream, emb, mean, (int)n, norms);
+  CM_TRY(hipGetLastError());
+  ClusterPairArgs pa;
+  pa.emb = emb; pa.labels = labels; pa.norms = norms; pa.mean = mean; pa.part = part;
+  pa.n = (int)n; pa.npad = rt * kTile; pa.ct = rt; pa.per = per;
+  hipLaunchKernelGGL(dad_cluster_pair, dim3(rt, nch), dim3(kThreads), 0, stream, pa);
+  CM_TRY(hipGetLastError());
+  ClusterRowArgs ra;
+  ra.emb = emb; ra.labels = labels; ra.part = part; ra.cent = cent; ra.hdr_i = hdr_i; ra.sil = sil;
+  ra.wpart = wpart; ra.silpart = silpart; ra.n = (int)n; ra.npad = rt * kTile; ra.chunks = nch;
+  hipLaunchKernelGGL(dad_cluster_rows, dim3(rt), dim3(kThreads), 0, stream, ra);
+  CM_TRY(hipGetLastError());
+  hipLaunchKernelGGL(dad_cluster_final, dim3(1), dim3(64), 0, stream, wpart, silpart, hdr_i, hdr_d, rt, out);
+  CM_TRY(hipGetLastError());
+  return DAD_OK;
+}
+
+extern "C" int dad_cluster_metrics(const float* emb, const int64_t* labels, int64_t n, double* out, float* sil,
+                                   void* workspace, void* stream) {
+  return dad_cluster_metrics_chunked(emb, labels, n, out, sil, 0, workspace, stream);
+}

@@ -14,7 +14,15 @@ For a split held in a FeatureStore, the whole-split forms do the same in one fus
 (dad_eval_split, csrc/eval_split.hip) and report the same values:
 
   validate_store, calibrate_anchors_store, embed_store, evaluate_store, EvalPlan, metrics_from_confusion
+
+and the class separation of a split's embeddings (dad_cluster_metrics, csrc/cluster.hip):
+
+  cluster_metrics, cluster_metrics_store, separation_report
+                      calculate_cluster_metrics / generate_analysis_report's `cluster_analysis`
+                      (I/iemocap_plot_tsne.py:390-398, 428-442)
 """
+import warnings
+
 import numpy as np
 import torch
 
@@ -186,6 +194,7 @@ class EvalPlan:
         self.result_d = torch.zeros(_RESULT_WORDS, dtype=torch.int64, device=dev)
         self.result_h = torch.zeros(_RESULT_WORDS, dtype=torch.int64).pin_memory()
         self._ws = None
+        self._cm = None
 
     @classmethod
     def of(cls, x):
@@ -203,6 +212,15 @@ class EvalPlan:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
+
+    def cluster_buffers(self):
+        """(workspace, result block on the device, pinned host copy) of dad_cluster_metrics over this
+        split, allocated at the first call and reused."""
+        if self._cm is None:
+            self._cm = (_cluster_workspace(self.n, self.device),
+                        torch.zeros(_lib.CM_SLOTS, dtype=torch.float64, device=self.device),
+                        torch.zeros(_lib.CM_SLOTS, dtype=torch.float64).pin_memory())
+        return self._cm
 
 
 def enqueue_eval_split(model, plan, use_teacher=False, use_entropy=True, precision="fp32", outputs=()):
@@ -251,6 +269,10 @@ def evaluate_store(model, plan_or_store, use_teacher=False, use_entropy=True, pr
     utterance has a non-finite logit."""
     plan = EvalPlan.of(plan_or_store)
     out = enqueue_eval_split(model, plan, use_teacher, use_entropy, precision, outputs)
+    return _read_eval_block(plan, out)
+
+
+def _read_eval_block(plan, out):
     stream = torch.cuda.current_stream(plan.device)
     plan.result_h.copy_(plan.result_d, non_blocking=True)
     stream.synchronize()
@@ -304,17 +326,34 @@ def metrics_from_confusion(cm):
 
 
 def validate_store(model, store_or_loader, domain_name="unknown", num_classes=4, teacher_disagreement=False,
-                   precision="fp32"):
+                   precision="fp32", cluster_metrics=False):
     """validate() over a FeatureStore split in one fused pass: the same dict, 'disagreement_rate'
-    from the same pass (the teacher runs on the student's row reads)."""
+    from the same pass (the teacher runs on the student's row reads).  With cluster_metrics the dict
+    gains 'silhouette_score' and 'calinski_harabasz_score' of the same pass's student embeddings
+    (dad_cluster_metrics behind dad_eval_split on the stream; (0.0, 0.0) and a warning for a label
+    configuration the scores are not defined for)."""
     if num_classes != 4:
         raise ValueError("the MI355X kernels are built for 4 classes")
     model.eval()
-    r = evaluate_store(model, store_or_loader, use_teacher=teacher_disagreement, precision=precision)
+    if not cluster_metrics:
+        r = evaluate_store(model, store_or_loader, use_teacher=teacher_disagreement, precision=precision)
+    else:
+        plan = EvalPlan.of(store_or_loader)
+        if plan.labels_d is None:
+            raise ValueError("the split has no labels")
+        out = enqueue_eval_split(model, plan, teacher_disagreement, True, precision, ("emb",))
+        ws, block_d, block_h = plan.cluster_buffers()
+        _enqueue_cluster(out["emb"], plan.labels_d, block_d, None, ws)
+        block_h.copy_(block_d, non_blocking=True)
+        r = _read_eval_block(plan, {})          # (synchronises the stream: both blocks are on the host)
+        cm = _cluster_result(block_h.numpy().copy())
     res = {}
     if teacher_disagreement:
         res["disagreement_rate"] = r["disagree"] / r["n"]
     res.update(metrics_from_confusion(r["confusion_student"]))
+    if cluster_metrics:
+        res["silhouette_score"] = cm["silhouette_score"]
+        res["calinski_harabasz_score"] = cm["calinski_harabasz_score"]
     return res
 
 
@@ -342,3 +381,134 @@ def embed_store(model, store_or_loader, use_teacher=False):
     model.eval()
     name = "t_emb" if use_teacher else "emb"
     return evaluate_store(model, store_or_loader, use_teacher=use_teacher, outputs=(name,))[name]
+
+
+# ------------------------------------------------------------------ class separation of a split
+# calculate_cluster_metrics (I/iemocap_plot_tsne.py:390-398) copies the embeddings to the host and
+# calls scikit-learn's silhouette_score and calinski_harabasz_score, O(n^2 * 256) each weight set.
+# dad_cluster_metrics (csrc/cluster.hip) computes both on the device from the embeddings
+# dad_eval_split leaves there; one copy of 16 doubles returns them.
+
+def _cluster_workspace(n, device):
+    fn = _lib.require("dad_cluster_workspace_bytes", "cluster_metrics")
+    need = int(fn(int(n)))
+    if need == 0:
+        raise ValueError("cluster metrics take 1 <= n <= %d rows, got %d" % (_lib.CM_MAX_N, n))
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _enqueue_cluster(emb, labels, block, sil, ws, chunks=0):
+    """dad_cluster_metrics on the current stream, enqueue only.  chunks > 0 asks for that many column
+    chunks per row tile instead of the planner's (dad_cluster_metrics_chunked: the tests' way to run
+    the chunked summation at small n)."""
+    n = emb.shape[0]
+    stream = torch.cuda.current_stream(emb.device).cuda_stream
+    if chunks:
+        fn = _lib.require("dad_cluster_metrics_chunked", "cluster_metrics")
+        rc = fn(_lib.ptr(emb), _lib.ptr(labels), n, _lib.ptr(block), _lib.ptr(sil), int(chunks), _lib.ptr(ws), stream)
+    else:
+        fn = _lib.require("dad_cluster_metrics", "cluster_metrics")
+        rc = fn(_lib.ptr(emb), _lib.ptr(labels), n, _lib.ptr(block), _lib.ptr(sil), _lib.ptr(ws), stream)
+    _lib.check(rc, "dad_cluster_metrics")
+
+
+def _cluster_result(block):
+    """The dict of cluster_metrics from the host copy of the DAD_CM_* block."""
+    nbad = int(block[_lib.CM_NONFINITE])
+    if nbad > 0:
+        raise _lib.DadError("dad_cluster_metrics: %d of %d labelled row(s) have a non-finite embedding component"
+                            % (nbad, int(block[_lib.CM_M])))
+    valid = bool(block[_lib.CM_VALID])
+    res = {
+        "silhouette_score": float(block[_lib.CM_SILHOUETTE]),
+        "calinski_harabasz_score": float(block[_lib.CM_CH]),
+        "valid": valid, "n_labelled": int(block[_lib.CM_M]), "classes_present": int(block[_lib.CM_K]),
+        "class_counts": [int(v) for v in block[_lib.CM_COUNTS:_lib.CM_COUNTS + 4]],
+        "silhouette_per_class": [float(v) for v in block[_lib.CM_SIL_CLASS:_lib.CM_SIL_CLASS + 4]],
+        "within": float(block[_lib.CM_W]), "between": float(block[_lib.CM_B]),
+        "block": block,
+    }
+    if not valid:
+        # scikit-learn raises here; calculate_cluster_metrics logs the warning and returns (0.0, 0.0)
+        warnings.warn("cluster metrics need 2 <= classes present <= labelled rows - 1, got %d classes over %d rows: "
+                      "both scores are 0.0" % (res["classes_present"], res["n_labelled"]), RuntimeWarning,
+                      stacklevel=3)
+    return res
+
+
+def cluster_metrics(emb, labels, samples=False, _chunks=0):
+    """calculate_cluster_metrics (I/iemocap_plot_tsne.py:390-398) on the device: scikit-learn's
+    silhouette_score and calinski_harabasz_score of emb [n, 256] (float32, device) under labels [n]
+    (int64; a host array is moved to the device), over the rows with a label in [0, 4).
+    Returns {'silhouette_score', 'calinski_harabasz_score', 'valid', 'n_labelled', 'classes_present',
+    'class_counts', 'silhouette_per_class', 'within', 'between'}; samples=True adds the device tensor
+    'silhouette_samples' [n] (0 for an unlabelled row).  Where scikit-learn would raise (fewer than 2
+    classes present, or as many classes as labelled rows) both scores are 0.0, 'valid' is False and a
+    RuntimeWarning is issued.  Raises DadError when a labelled row has a non-finite component."""
+    if not torch.is_tensor(emb) or not emb.is_cuda or emb.dtype != torch.float32 or emb.dim() != 2 \
+            or emb.shape[1] != 256:
+        raise ValueError("emb must be a float32 device tensor [n, 256]")
+    emb = emb.contiguous()
+    labels = torch.as_tensor(labels).to(device=emb.device, dtype=torch.int64).contiguous()
+    if labels.shape != (emb.shape[0],):
+        raise ValueError("labels must be [n]")
+    n = emb.shape[0]
+    ws = _cluster_workspace(n, emb.device)
+    block = torch.empty(_lib.CM_SLOTS, dtype=torch.float64, device=emb.device)
+    sil = torch.empty(n, dtype=torch.float32, device=emb.device) if samples else None
+    _enqueue_cluster(emb, labels, block, sil, ws, _chunks)
+    res = _cluster_result(block.cpu().numpy())
+    if samples:
+        res["silhouette_samples"] = sil
+    return res
+
+
+def enqueue_cluster_metrics_store(model, plan, use_teacher=False, precision="fp32", samples=False):
+    """The enqueue part of cluster_metrics_store (no copy, no synchronisation; graph-capturable):
+    dad_eval_split for the embeddings, dad_cluster_metrics behind it on the current stream against the
+    plan's device labels.  The block lands in plan.cluster_buffers()[1].  Returns (emb, sil or None)."""
+    if plan.labels_d is None:
+        raise ValueError("the split has no labels")
+    name = "t_emb" if use_teacher else "emb"
+    emb = enqueue_eval_split(model, plan, use_teacher=use_teacher, precision=precision, outputs=(name,))[name]
+    ws, block_d, _ = plan.cluster_buffers()
+    sil = torch.empty(plan.n, dtype=torch.float32, device=plan.device) if samples else None
+    _enqueue_cluster(emb, plan.labels_d, block_d, sil, ws)
+    return emb, sil
+
+
+def cluster_metrics_store(model, store_or_loader, use_teacher=False, precision="fp32", samples=False):
+    """cluster_metrics of the split's eval-mode embeddings (the teacher's with use_teacher) without
+    their leaving the device: one dad_eval_split, one dad_cluster_metrics, one copy of the block.
+    The workspace is cached on the split's EvalPlan."""
+    model.eval()
+    plan = EvalPlan.of(store_or_loader)
+    _, sil = enqueue_cluster_metrics_store(model, plan, use_teacher, precision, samples)
+    _, block_d, block_h = plan.cluster_buffers()
+    block_h.copy_(block_d, non_blocking=True)
+    torch.cuda.current_stream(plan.device).synchronize()
+    res = _cluster_result(block_h.numpy().copy())
+    if samples:
+        res["silhouette_samples"] = sil
+    return res
+
+
+def separation_from_metrics(initial, trained):
+    """generate_analysis_report's `cluster_analysis` block (I/iemocap_plot_tsne.py:428-442) from the
+    two (silhouette, CH) pairs or cluster_metrics dicts; every value a Python float."""
+    pair = lambda r: ((r["silhouette_score"], r["calinski_harabasz_score"]) if isinstance(r, dict) else r)
+    (si, ci), (st, ct) = pair(initial), pair(trained)
+    si, ci, st, ct = float(si), float(ci), float(st), float(ct)
+    return {
+        "initial_weights": {"silhouette_score": si, "calinski_harabasz_score": ci},
+        "trained_weights": {"silhouette_score": st, "calinski_harabasz_score": ct},
+        "improvement": {"silhouette_improvement": st - si, "calinski_improvement": ct - ci,
+                        "silhouette_percentage": (st - si) / abs(si) * 100 if si != 0 else 0.0},
+    }
+
+
+def separation_report(initial_model, trained_model, store_or_loader):
+    """The reference's `cluster_analysis` block for one split under the initial and the trained
+    weights (student embeddings, as iemocap_plot_tsne.py embeds with)."""
+    return separation_from_metrics(cluster_metrics_store(initial_model, store_or_loader),
+                                   cluster_metrics_store(trained_model, store_or_loader))
