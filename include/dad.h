@@ -264,10 +264,11 @@ int dad_step_prepare_rows(const dad_config* cfg, const dad_batch* batch, void* w
  * the step itself enqueues from -- when its backward is dad_step_backward_ahead_split(.., next_cfg,
  * next_batch, defer, ..) (next_cfg = next_batch = NULL, defer = 0: dad_step_backward).  No device call;
  * the batch pointers are only tested for NULL, never followed.  A grid of 0 = that launch is not made;
- * kernel names are static strings; dad_tail_ecda_w, dad_wgrad_direct[_f16]_cps (and the standalone dad_prep)
- * also stand for their `_s16` siblings, the same kernels with the row loads in an fp16 / bf16 store's type,
- * which the step launches in their place, with the same grids, when the rows that launch prepares lie in a
- * 16-bit store (ABI 10).  Returns cfg's validation code, or DAD_E_ARG for cus < 2, out = NULL
+ * kernel names are static strings and name families: the plan resolves every launch to its exact entry point
+ * (dad_step_plan_kernels below), and this struct reports the kernel that entry point stands in for -- itself,
+ * or for an `_s16` sibling (the same kernel with the row loads in an fp16 / bf16 store's type, ABI 10) and
+ * an `_rg` sibling (a ragged step's kernel) the f32 / dense kernel of the same grid.  This query has no
+ * current batch: it plans for a padded f32 one.  Returns cfg's validation code, or DAD_E_ARG for cus < 2, out = NULL
  * or defer bits outside DAD_PREP_*; a next step that does not qualify for preparation ahead is no
  * error (prepped = 0).  Diagnostics and tests. */
 typedef struct dad_step_plan_info {
@@ -291,6 +292,15 @@ typedef struct dad_step_plan_info {
 } dad_step_plan_info;
 int dad_step_plan(const dad_config* cfg, const dad_config* next_cfg, const dad_batch* next_batch, int defer,
                   int cus, dad_step_plan_info* out);
+/* Host-only (ABI 10, added without a bump): the exact entry points of the same plan, the `_s16` / `_rg`
+ * siblings named as such, in launch order; out[i] = NULL where that launch is not made.  `batch` is this
+ * step's (its row types choose the standalone preparation; only the struct's own fields are read), or NULL
+ * for a padded f32 batch.  Static strings, no device call.  Returns dad_step_plan's codes, and
+ * for a batch whose row types the step refuses the step's code (DAD_E_ARG / DAD_E_UNSUPPORTED).
+ * Diagnostics and tests. */
+#define DAD_STEP_LAUNCHES 6   /* prep, encode, pool, tail, wgrad, reduce: launch order */
+int dad_step_plan_kernels(const dad_config* cfg, const dad_batch* batch, const dad_config* next_cfg,
+                          const dad_batch* next_batch, int defer, int cus, const char* out[DAD_STEP_LAUNCHES]);
 /* Host-only: how a ragged step (cfg->ragged = 1, see dad_config) on a device of `cus` compute units divides
  * its live slabs, computed from HOST copies of the two length arrays (lenc [B], lenn [Bn]; lenn may be NULL
  * in a warm-up step) by the functions the kernels call on the device lengths.  Live lists: teachers run the

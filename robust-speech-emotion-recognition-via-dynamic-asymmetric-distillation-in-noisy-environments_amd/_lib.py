@@ -21,6 +21,7 @@ PREC_FP32, PREC_BF16, PREC_FP16 = 0, 1, 2
 DRAW_WEAK, DRAW_STRONG, DRAW_FEAT_KEEP, DRAW_TSTART, DRAW_KEEP1, DRAW_KEEP2 = range(1, 7)
 RNG_EXPLICIT, RNG_COUNTER = 0, 1
 PREP_CLEAN, PREP_NOISY = 1, 2     # dad.h DAD_PREP_* (dad_step_backward_ahead_split / dad_step_prepare_rows)
+STEP_LAUNCHES = 6                 # dad.h DAD_STEP_LAUNCHES (dad_step_plan_kernels): prep, encode, pool, tail, wgrad, reduce
 STORE_F32, STORE_F16, STORE_BF16 = 0, 1, 2   # dad.h DAD_STORE_* (dad_collate, dad_batch.xc_dtype / xn_dtype)
 E_ARG, E_SHAPE, E_COMM, E_UNSUPPORTED = 1001, 1002, 1003, 1004   # dad.h DAD_E_*
 
@@ -135,6 +136,9 @@ EXPORTS = {
                                              ctypes.c_void_p, ctypes.c_int]),
     "dad_step_plan": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.POINTER(DadConfig), ctypes.POINTER(DadBatch),
                                      ctypes.c_int, ctypes.c_int, ctypes.POINTER(DadStepPlanInfo)]),
+    "dad_step_plan_kernels": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.POINTER(DadBatch),
+                                             ctypes.POINTER(DadConfig), ctypes.POINTER(DadBatch), ctypes.c_int,
+                                             ctypes.c_int, ctypes.POINTER(ctypes.c_char_p)]),
     "dad_step_ragged_plan": (ctypes.c_int, [ctypes.POINTER(DadConfig), ctypes.POINTER(ctypes.c_int32),
                                             ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
                                             ctypes.POINTER(DadRaggedPlan)]),
@@ -210,7 +214,7 @@ EXPORTS = {
 
 # Entry points added without an ABI bump: a library of the same ABI version built before them loads, and
 # the feature that needs one reports the stale build when it is asked for (require()).
-OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_trace_bytes", "dad_trace_append",
+OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_step_plan_kernels", "dad_trace_bytes", "dad_trace_append",
                     "dad_cluster_workspace_bytes", "dad_cluster_metrics", "dad_cluster_plan",
                     "dad_cluster_metrics_chunked")
 

@@ -18,20 +18,6 @@ int device_cus(int* out) {
   return DAD_OK;
 }
 
-// the standalone preparation's kernel: the ragged sibling, the 16-bit-store sibling, or dad_prep
-static void (*prep_kernel_of(const DadPrepArgs& p, bool ragged))(DadPrepArgs) {
-  return ragged ? dad_prep_rg : dad_prep_s16_needed(p) ? dad_prep_s16 : dad_prep;
-}
-
-int launch_prep(const DadPrepArgs& p, hipStream_t stream, bool ragged) {
-  int cus = 0;
-  const int rc = device_cus(&cus);
-  if (rc) return rc;
-  hipLaunchKernelGGL(prep_kernel_of(p, ragged), dim3(prep_grid_of(cus)), dim3(DAD_PREP_THREADS), 0, stream, p);
-  DAD_TRY(hipGetLastError());
-  return DAD_OK;
-}
-
 namespace {
 
 inline DadStoreRows store_rows_of(const dad_batch* bt) { return DadStoreRows{bt->rowc, bt->lenc, bt->rown, bt->lenn}; }
@@ -80,35 +66,182 @@ int check_next_batch(const dad_config* ncfg, const dad_batch* nbt) {
   return check_batch_dtypes(ncfg, nbt);
 }
 
+// dad_step_plan / dad_step_plan_kernels: their arguments checked, then the plan the step enqueues from
+int plan_query(const dad_config* cfg, const dad_batch* batch, const dad_config* next_cfg, const dad_batch* next_batch,
+               int defer, int cus, bool has_out, StepPlan* plan) {
+  const int rc = check_cfg(cfg);
+  if (rc) return rc;
+  if (cus < 2 || !has_out || (defer & ~(DAD_PREP_CLEAN | DAD_PREP_NOISY)) != 0) return DAD_E_ARG;
+  const int brc = batch ? check_batch_dtypes(cfg, batch) : DAD_OK;
+  if (brc) return brc;
+  const int nrc = check_next_batch(next_cfg, next_batch);
+  if (nrc) return nrc;
+  *plan = plan_step(cfg, batch, next_cfg, next_batch, defer, cus);
+  return plan->encode_rc;
+}
+
 // p restricted to `parts` (DAD_PREP_*) of its set
 void prep_only(DadPrepArgs& p, int parts) {
   p.clean = (parts & DAD_PREP_CLEAN) ? 1 : 0;
   if (!(parts & DAD_PREP_NOISY)) p.warmup = 1;   // (dad_prep_rows: no noisy rows in a warm-up set)
 }
 
-// How each planned kernel (step_plan.h StepKernel) is launched: entry point and block size.
-struct EncodeLaunch { void (*kernel)(DadEncodeArgs); int threads; };
-const EncodeLaunch kEncodeLaunch[] = {   // [plan.encode - K_ENCODE_F32]
-    {dad_encode_f32, DAD_ENC_F32_THREADS}, {dad_encode_wp, DAD_ENC_WS_THREADS}, {dad_encode_wp_f16, DAD_ENC_WS_THREADS}};
-// (cp: the variants that also take the next batch's clean rows)
-struct WgradLaunch {
-  void (*kernel)(DadWgradArgs, DadReduceArgs);
-  void (*cp)(DadWgradArgs, DadReduceArgs, DadPrepArgs);
-  int threads;
+// The regions of a step's workspace (dad_ws_layout), carved once.
+struct StepWs {
+  float *part_sum, *part_cnt, *vlen, *cnt_tot, *ge, *ge_ecda, *normpart, *ecda, *gzb, *gflat, *wpart;
+  uint32_t *bits, *eflag, *pool_ready;
+  // 16-bit modes: the two prepared sets.  A step reads the one of its counter's parity; the next step's
+  // is the other one, so preparing it in this step's launches leaves this one intact for wgrad.
+  uint16_t* x16[2];
+  StepWs(void* ws, const DadWs& L)
+      : part_sum(ws_ptr<float>(ws, L.part_sum)), part_cnt(ws_ptr<float>(ws, L.part_cnt)),
+        vlen(ws_ptr<float>(ws, L.vlen)), cnt_tot(ws_ptr<float>(ws, L.cnt_tot)), ge(ws_ptr<float>(ws, L.ge)),
+        ge_ecda(ws_ptr<float>(ws, L.ge_ecda)), normpart(ws_ptr<float>(ws, L.normpart)),
+        ecda(ws_ptr<float>(ws, L.ecda)), gzb(ws_ptr<float>(ws, L.gzb)), gflat(ws_ptr<float>(ws, L.gflat)),
+        wpart(ws_ptr<float>(ws, L.wpart)), bits(ws_ptr<uint32_t>(ws, L.bits)), eflag(ws_ptr<uint32_t>(ws, L.eflag)),
+        pool_ready(ws_ptr<uint32_t>(ws, L.ready)),
+        x16{ws_ptr<uint16_t>(ws, L.xs16), ws_ptr<uint16_t>(ws, L.xs16 + L.x16set)} {}
+  uint16_t* set_of(const dad_config* c) const { return x16[c->counter & 1u]; }
 };
-const WgradLaunch kWgradLaunch[] = {   // [plan.wgrad - K_WGRAD_F32]
-    {dad_wgrad_f32, nullptr, DAD_WGRAD_THREADS},
-    {dad_wgrad_direct, nullptr, WGD_THREADS}, {nullptr, dad_wgrad_direct_cp, WGD_THREADS},
-    {nullptr, dad_wgrad_direct_cps, WGD_THREADS},
-    {dad_wgrad_direct_f16, nullptr, WGD_THREADS}, {nullptr, dad_wgrad_direct_f16_cp, WGD_THREADS},
-    {nullptr, dad_wgrad_direct_f16_cps, WGD_THREADS}};
-// the ragged step's siblings (dad_kernels.h `_rg`) of the 16-bit kernels above
-const EncodeLaunch kEncodeLaunchRg[] = {   // [plan.encode - K_ENCODE_WP]
-    {dad_encode_wp_rg, DAD_ENC_WS_THREADS}, {dad_encode_wp_f16_rg, DAD_ENC_WS_THREADS}};
-const WgradLaunch kWgradLaunchRg[2] = {    // [fp16]: plain, and with the (ragged, store) next batch's clean rows
-    {dad_wgrad_direct_rg, dad_wgrad_direct_cps_rg, WGD_THREADS}, {dad_wgrad_direct_f16_rg, dad_wgrad_direct_f16_cps_rg, WGD_THREADS}};
-struct ReduceLaunch { void (*kernel)(DadReduceArgs); int threads; };
-const ReduceLaunch kReduceLaunch[] = {{dad_reduce, DAD_REDUCE_THREADS}, {dad_reduce_w, 64}};   // [plan.reduce - K_REDUCE]
+
+// What the argument blocks of one step are filled from.
+struct Step {
+  const dad_config* cfg;
+  const dad_batch* bt;
+  const dad_state* st;
+  const StepPlan& plan;
+  DadGeom G;
+  Keys k;
+  StepWs ws;
+  Step(const dad_config* c, const dad_batch* b, const dad_state* s, const StepPlan& p, void* workspace)
+      : cfg(c), bt(b), st(s), plan(p), G(geom_of(c)), k(keys_of(c)),
+        ws(workspace, dad_ws_layout(G, p.max_splits, c->precision)) {}
+  bool explicit_rng() const { return cfg->rng_mode == DAD_RNG_EXPLICIT; }
+};
+
+// 1. fused augmentation + encoder GEMMs + pooling partials
+DadEncodeArgs encode_args(const Step& s) {
+  const dad_config* cfg = s.cfg;
+  const dad_batch* bt = s.bt;
+  DadEncodeArgs ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.g = s.G; ea.warmup = cfg->warmup;
+  ea.mask_len = cfg->mask_len; ea.start_hi = cfg->start_hi;
+  // (the FP32 encoder reads the rows, f32 by check_batch_dtypes; the 16-bit ones read the prepared set)
+  ea.xc = static_cast<const float*>(bt->xc); ea.mc = bt->mc; ea.xn = static_cast<const float*>(bt->xn); ea.mn = bt->mn;
+  ea.src = store_rows_of(bt);
+  ea.w1_student = s.st->student + DAD_OFF_W1; ea.b1_student = s.st->student + DAD_OFF_B1;
+  ea.w1_teacher = s.st->teacher + DAD_OFF_W1; ea.b1_teacher = s.st->teacher + DAD_OFF_B1;
+  ea.w1h_student = s.st->w1bf_student;
+  ea.w1h_teacher = s.st->w1bf_teacher;
+  ea.pool_ready = s.ws.pool_ready;
+  if (s.explicit_rng()) { ea.nw = bt->nw; ea.ns = bt->ns; ea.u = bt->u; ea.start = bt->start; }
+  ea.key_weak = s.k.weak; ea.key_strong = s.k.strong; ea.key_feat = s.k.feat; ea.key_tstart = s.k.tstart;
+  ea.weak_std = cfg->weak_std; ea.strong_std = cfg->strong_std; ea.feat_p = cfg->feat_p;
+  ea.part_sum = s.ws.part_sum; ea.part_cnt = s.ws.part_cnt; ea.bits = s.ws.bits;
+  ea.ws_nt = s.plan.ws_nt; ea.ws_ns = s.plan.ws_ns;
+  const size_t nrc = (size_t)s.G.Bc * s.G.Tc, nrn = (size_t)s.G.Bn * s.G.Tn;
+  ea.x16c = s.ws.set_of(cfg); ea.x16s = ea.x16c + nrc * DAD_D; ea.x16w = ea.x16s + (cfg->warmup ? 0 : nrn) * DAD_D;
+  return ea;
+}
+
+// 2. pooled embeddings + classifier logits: a launch of its own, or the spare blocks of the
+//    wave-centric tail launch (pa.ready: its arrival counters, zeroed by this step's encoder)
+DadPoolArgs pool_args(const Step& s) {
+  const dad_config* cfg = s.cfg;
+  const dad_batch* bt = s.bt;
+  DadPoolArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.g = s.G; pa.warmup = cfg->warmup;
+  pa.mc = bt->mc; pa.mn = bt->mn; pa.part_sum = s.ws.part_sum;
+  pa.student = s.st->student; pa.teacher = s.st->teacher;
+  if (s.explicit_rng()) { pa.keep1 = bt->keep1; pa.keep2 = bt->keep2; }
+  pa.key_drop1 = s.k.drop1; pa.key_drop2 = s.k.drop2;
+  pa.p_drop = cfg->p_drop; pa.drop_scale = cfg->drop_scale;
+  pa.emb = s.st->emb; pa.vlen = s.ws.vlen; pa.logits = s.st->logits;
+  pa.part_cnt = s.ws.part_cnt; pa.cnt_tot = s.ws.cnt_tot;
+  pa.eflag = s.ws.eflag; pa.tail_terms = s.st->tail + DAD_T_ECDA_TERM;
+  pa.range_flag = reinterpret_cast<uint32_t*>(s.st->tail + DAD_T_RANGE);
+  if (cfg->ragged) { pa.lenc = bt->lenc; pa.lenn = bt->lenn; }
+  if (!s.plan.pool_grid) pa.ready = s.ws.pool_ready;
+  return pa;
+}
+
+// 3. losses, DACP mask, analytic backward to dL/de and the classifier grads
+DadTailArgs tail_args(const Step& s) {
+  DadTailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.cfg = *s.cfg; ta.yc = s.bt->yc; ta.logits = s.st->logits; ta.emb = s.st->emb; ta.student = s.st->student;
+  if (s.explicit_rng()) { ta.keep1 = s.bt->keep1; ta.keep2 = s.bt->keep2; }
+  ta.key_drop1 = s.k.drop1; ta.key_drop2 = s.k.drop2;
+  ta.dacp = s.st->dacp; ta.tailf = s.st->tail; ta.ge = s.ws.ge; ta.ge_ecda = s.ws.ge_ecda; ta.grad = s.st->grad;
+  ta.gzb = s.ws.gzb; ta.eflag = s.ws.eflag;
+  return ta;
+}
+
+// 4. ECDA (class-aware MMD + compactness + repulsion) and its embedding grads: after the
+//    warm-up, in the same launch as the tail (block 0 = tail, blocks 1..C = classes)
+DadEcdaArgs ecda_args(const Step& s) {
+  DadEcdaArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.cfg = *s.cfg; ca.yc = s.bt->yc; ca.emb = s.st->emb; ca.tailf = s.st->tail;
+  ca.tail_terms = s.st->tail + DAD_T_ECDA_TERM; ca.ge = s.ws.ge_ecda; ca.scratch = s.ws.ecda; ca.eflag = s.ws.eflag;
+  ca.sink = s.ws.gflat;
+  return ca;
+}
+
+// 5. dW1 as one direct split-K GEMM (G = ReLU' * dL/de / len rebuilt from the tail's dL/dz
+//    and the ECDA rows), then the split sums with db1, dW2, loss totals, squared-norm partials
+DadWgradArgs wgrad_args(const Step& s) {
+  const dad_config* cfg = s.cfg;
+  const dad_batch* bt = s.bt;
+  DadWgradArgs wa;
+  memset(&wa, 0, sizeof(wa));
+  wa.g = s.G; wa.warmup = cfg->warmup;
+  wa.mask_len = cfg->mask_len; wa.start_hi = cfg->start_hi;
+  wa.xc = static_cast<const float*>(bt->xc); wa.xn = static_cast<const float*>(bt->xn);   // (FP32 only)
+  wa.src = store_rows_of(bt);
+  if (s.explicit_rng()) { wa.ns = bt->ns; wa.u = bt->u; wa.start = bt->start; }
+  wa.key_strong = s.k.strong; wa.key_feat = s.k.feat; wa.key_tstart = s.k.tstart;
+  wa.strong_std = cfg->strong_std; wa.feat_p = cfg->feat_p;
+  wa.bits = s.ws.bits; wa.ge = s.ws.ge; wa.vlen = s.ws.vlen; wa.xs16 = s.ws.set_of(cfg);
+  wa.splits = s.plan.splits; wa.ntiles = s.plan.wgrad_tiles;
+  wa.wpart = s.ws.wpart;
+  return wa;
+}
+
+DadReduceArgs reduce_args(const Step& s) {
+  const dad_config* cfg = s.cfg;
+  DadReduceArgs ra;
+  memset(&ra, 0, sizeof(ra));
+  ra.g = s.G; ra.warmup = cfg->warmup;
+  ra.want_norm = cfg->dp_world == 1;
+  ra.w_kl = cfg->w_kl; ra.w_ecda = cfg->w_ecda;
+  ra.ge_ecda = s.ws.ge_ecda;
+  ra.gzb = s.ws.gzb; ra.eflag = s.ws.eflag; ra.student = s.st->student; ra.emb = s.st->emb;
+  if (s.explicit_rng()) { ra.keep1 = s.bt->keep1; ra.keep2 = s.bt->keep2; }
+  ra.key_drop1 = s.k.drop1; ra.key_drop2 = s.k.drop2; ra.p_drop = cfg->p_drop; ra.drop_scale = cfg->drop_scale;
+  ra.ge = s.ws.ge; ra.vlen = s.ws.vlen; ra.cnt_tot = s.ws.cnt_tot; ra.tailf = s.st->tail;
+  ra.grad = s.st->grad; ra.normpart = s.ws.normpart;
+  ra.pool_abort = s.plan.pool_grid ? nullptr : s.ws.pool_ready + DAD_POOL_ABORT;
+  ra.splits = s.plan.splits; ra.wpart = s.ws.wpart;
+  return ra;
+}
+
+// The tail and the weight gradient, each with the argument blocks its kernel's class takes.
+int launch_tail(const Step& s, hipStream_t stream, const DadPrepArgs& next_rows, const DadPoolArgs& pa) {
+  const StepPlan& p = s.plan;
+  switch (kStepKernels[p.tail].sig) {
+    case SIG_TAIL: return launch(p.tail, p.tail_grid, stream, tail_args(s));
+    case SIG_TAIL_ECDA: return launch(p.tail, p.tail_grid, stream, tail_args(s), ecda_args(s));
+    default: return launch(p.tail, p.tail_grid, stream, tail_args(s), ecda_args(s), next_rows, pa);
+  }
+}
+int launch_wgrad(const Step& s, hipStream_t stream, const DadPrepArgs& next_clean, const DadReduceArgs& ra) {
+  const StepPlan& p = s.plan;
+  if (kStepKernels[p.wgrad].sig == SIG_WGRAD_CP) return launch(p.wgrad, p.wgrad_grid, stream, wgrad_args(s), ra, next_clean);
+  return launch(p.wgrad, p.wgrad_grid, stream, wgrad_args(s), ra);
+}
 
 }  // namespace
 
@@ -164,17 +297,25 @@ int dad_encoder_ws_jobs(const dad_config* cfg, int cus, int* jobs, int capacity)
 
 int dad_step_plan(const dad_config* cfg, const dad_config* next_cfg, const dad_batch* next_batch, int defer, int cus,
                   dad_step_plan_info* out) {
-  const int rc = check_cfg(cfg);
+  StepPlan p;
+  const int rc = plan_query(cfg, nullptr, next_cfg, next_batch, defer, cus, out != nullptr, &p);
   if (rc) return rc;
-  if (cus < 2 || !out || (defer & ~(DAD_PREP_CLEAN | DAD_PREP_NOISY)) != 0) return DAD_E_ARG;
-  const int nrc = check_next_batch(next_cfg, next_batch);
-  if (nrc) return nrc;
-  const StepPlan p = plan_step(cfg, next_cfg, next_batch, defer, cus);
-  if (p.encode_rc) return p.encode_rc;
   *out = dad_step_plan_info{p.splits, p.max_splits, p.prep_grid, p.encode_grid, p.ws_nt, p.ws_ns, p.pool_grid,
                             p.tail_grid, p.tail_prep, p.tail_prep == DAD_PREP_CLEAN, p.wgrad_grid, p.wgrad_clean,
-                            p.wgrad_store, p.reduce_grid, p.prepped, p.pending, kStepKernelName[p.encode],
-                            kStepKernelName[p.tail], kStepKernelName[p.wgrad], kStepKernelName[p.reduce]};
+                            p.wgrad_store, p.reduce_grid, p.prepped, p.pending, family_name(p.encode),
+                            family_name(p.tail), family_name(p.wgrad), family_name(p.reduce)};
+  return DAD_OK;
+}
+
+int dad_step_plan_kernels(const dad_config* cfg, const dad_batch* batch, const dad_config* next_cfg,
+                          const dad_batch* next_batch, int defer, int cus, const char* out[DAD_STEP_LAUNCHES]) {
+  StepPlan p;
+  const int rc = plan_query(cfg, batch, next_cfg, next_batch, defer, cus, out != nullptr, &p);
+  if (rc) return rc;
+  const struct { StepKernel kernel; int grid; } launches[DAD_STEP_LAUNCHES] = {
+      {p.prep, p.prep_grid}, {p.encode, p.encode_grid}, {p.pool, p.pool_grid},
+      {p.tail, p.tail_grid}, {p.wgrad, p.wgrad_grid}, {p.reduce, p.reduce_grid}};
+  for (int i = 0; i < DAD_STEP_LAUNCHES; ++i) out[i] = launches[i].grid ? kStepKernels[launches[i].kernel].name : nullptr;
   return DAD_OK;
 }
 
@@ -196,189 +337,67 @@ int dad_workspace_bytes(const dad_config* cfg, size_t* bytes) {
 
 }  // extern "C"
 
-// The launches of one step: validate, plan (step_plan.h), fill the argument blocks, launch what the
-// plan says.  (ncfg, nbt, defer): dad_step_backward_ahead_split's next batch and deferred parts.
+// dad_step_backward_ahead[_split]'s request: the next step, the DAD_PREP_* parts of its rows left to the
+// caller, and where to report what was enqueued
+struct Ahead {
+  const dad_config* cfg;
+  const dad_batch* batch;
+  int defer;
+  int* prepped;
+  int* pending;
+};
+
+// The launches of one step: validate, plan (step_plan.h), carve the workspace, fill the argument blocks,
+// launch what the plan says in its order.
 static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const dad_state* st, void* workspace,
-                               void* stream_, bool do_encode, bool do_backward, const dad_config* ncfg = nullptr,
-                               const dad_batch* nbt = nullptr, int* prepped = nullptr, int defer = 0,
-                               int* pending = nullptr) {
-  if (prepped) *prepped = 0;
-  if (pending) *pending = 0;
+                               void* stream_, bool do_encode, bool do_backward, const Ahead& ahead = Ahead{}) {
+  if (ahead.prepped) *ahead.prepped = 0;
+  if (ahead.pending) *ahead.pending = 0;
   int rc = check_step_args(cfg, bt, st, workspace);
   if (rc) return rc;
-  rc = check_next_batch(ncfg, nbt);
+  rc = check_next_batch(ahead.cfg, ahead.batch);
   if (rc) return rc;
   int cus = 0;
   rc = device_cus(&cus);
   if (rc) return rc;
-  const StepPlan plan = plan_step(cfg, ncfg, nbt, defer, cus);
-
-  const bool explicit_rng = cfg->rng_mode == DAD_RNG_EXPLICIT;
-  const DadStoreRows src = store_rows_of(bt);
+  const StepPlan plan = plan_step(cfg, bt, ahead.cfg, ahead.batch, ahead.defer, cus);
+  const Step s(cfg, bt, st, plan, workspace);
   hipStream_t stream = (hipStream_t)stream_;
-  const DadGeom G = geom_of(cfg);
-  const DadWs L = dad_ws_layout(G, plan.max_splits, cfg->precision);
-  const Keys k = keys_of(cfg);
-  float* part_sum = ws_ptr<float>(workspace, L.part_sum);
-  float* part_cnt = ws_ptr<float>(workspace, L.part_cnt);
-  uint32_t* bits = ws_ptr<uint32_t>(workspace, L.bits);
-  float* vlen = ws_ptr<float>(workspace, L.vlen);
-  float* cnt_tot = ws_ptr<float>(workspace, L.cnt_tot);
-  float* ge = ws_ptr<float>(workspace, L.ge);
-  float* ge_ecda = ws_ptr<float>(workspace, L.ge_ecda);
-  float* normpart = ws_ptr<float>(workspace, L.normpart);
-  float* ecda_scratch = ws_ptr<float>(workspace, L.ecda);
-  float* gzb = ws_ptr<float>(workspace, L.gzb);
-  uint32_t* eflag = ws_ptr<uint32_t>(workspace, L.eflag);
-  uint32_t* pool_ready = ws_ptr<uint32_t>(workspace, L.ready);
-  // 16-bit modes: this step's prepared set (parity of the step counter; the next step's set is
-  // the other one, so preparing it in this step's launches leaves this one intact for wgrad)
-  uint16_t* xs16 = ws_ptr<uint16_t>(workspace, L.xs16 + (cfg->counter & 1u) * L.x16set);
-  const size_t nrc = (size_t)G.Bc * G.Tc, nrn = (size_t)G.Bn * G.Tn;
 
-  // 1. fused augmentation + encoder GEMMs + pooling partials
   if (do_encode) {
     if (plan.encode_rc) return plan.encode_rc;
-    DadEncodeArgs ea;
-    memset(&ea, 0, sizeof(ea));
-    ea.g = G; ea.warmup = cfg->warmup;
-    ea.mask_len = cfg->mask_len; ea.start_hi = cfg->start_hi;
-    // (the FP32 encoder reads the rows, f32 by check_batch_dtypes; the 16-bit ones read the prepared set)
-    ea.xc = static_cast<const float*>(bt->xc); ea.mc = bt->mc; ea.xn = static_cast<const float*>(bt->xn); ea.mn = bt->mn;
-    ea.src = src;
-    ea.w1_student = st->student + DAD_OFF_W1; ea.b1_student = st->student + DAD_OFF_B1;
-    ea.w1_teacher = st->teacher + DAD_OFF_W1; ea.b1_teacher = st->teacher + DAD_OFF_B1;
-    ea.w1h_student = st->w1bf_student;
-    ea.w1h_teacher = st->w1bf_teacher;
-    ea.pool_ready = pool_ready;
-    if (explicit_rng) { ea.nw = bt->nw; ea.ns = bt->ns; ea.u = bt->u; ea.start = bt->start; }
-    ea.key_weak = k.weak; ea.key_strong = k.strong; ea.key_feat = k.feat; ea.key_tstart = k.tstart;
-    ea.weak_std = cfg->weak_std; ea.strong_std = cfg->strong_std; ea.feat_p = cfg->feat_p;
-    ea.part_sum = part_sum; ea.part_cnt = part_cnt; ea.bits = bits;
-    ea.ws_nt = plan.ws_nt; ea.ws_ns = plan.ws_ns;
-    ea.x16c = xs16; ea.x16s = xs16 + nrc * DAD_D; ea.x16w = ea.x16s + (cfg->warmup ? 0 : nrn) * DAD_D;
     tk_begin();
     tk_mark(TK_E0, stream);
-    if (plan.prep_grid) {
-      const DadPrepArgs own = prep_args(cfg, bt, xs16);
-      hipLaunchKernelGGL(prep_kernel_of(own, cfg->ragged != 0), dim3(plan.prep_grid), dim3(DAD_PREP_THREADS), 0, stream,
-                         own);
-      DAD_TRY(hipGetLastError());
-    }
-    const EncodeLaunch& enc = cfg->ragged ? kEncodeLaunchRg[plan.encode - K_ENCODE_WP] : kEncodeLaunch[plan.encode - K_ENCODE_F32];
-    hipLaunchKernelGGL(enc.kernel, dim3(plan.encode_grid), dim3(enc.threads), 0, stream, ea);
-    DAD_TRY(hipGetLastError());
+    if (plan.prep_grid) DAD_RET(launch(plan.prep, plan.prep_grid, stream, prep_args(cfg, bt, s.ws.set_of(cfg))));
+    DAD_RET(launch(plan.encode, plan.encode_grid, stream, encode_args(s)));
     tk_mark(TK_E1, stream);
   }
   if (!do_backward) return DAD_OK;
-  if (prepped) *prepped = plan.prepped;
-  if (pending) *pending = plan.pending;
+  if (ahead.prepped) *ahead.prepped = plan.prepped;
+  if (ahead.pending) *ahead.pending = plan.pending;
 
-  // 2. pooled embeddings + classifier logits: a launch of its own, or the spare blocks of the
-  //    wave-centric tail launch (no pool timing point then: that launch is timed from the encoder's end)
-  DadPoolArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.g = G; pa.warmup = cfg->warmup;
-  pa.mc = bt->mc; pa.mn = bt->mn; pa.part_sum = part_sum;
-  pa.student = st->student; pa.teacher = st->teacher;
-  if (explicit_rng) { pa.keep1 = bt->keep1; pa.keep2 = bt->keep2; }
-  pa.key_drop1 = k.drop1; pa.key_drop2 = k.drop2;
-  pa.p_drop = cfg->p_drop; pa.drop_scale = cfg->drop_scale;
-  pa.emb = st->emb; pa.vlen = vlen; pa.logits = st->logits;
-  pa.part_cnt = part_cnt; pa.cnt_tot = cnt_tot;
-  pa.eflag = eflag; pa.tail_terms = st->tail + DAD_T_ECDA_TERM;
-  pa.range_flag = reinterpret_cast<uint32_t*>(st->tail + DAD_T_RANGE);
-  if (cfg->ragged) { pa.lenc = bt->lenc; pa.lenn = bt->lenn; }
+  // (no pool timing point when the tail launch pools: that launch is timed from the encoder's end)
+  const DadPoolArgs pa = pool_args(s);
   if (plan.pool_grid) {
-    hipLaunchKernelGGL(cfg->ragged ? dad_pool_rg : dad_pool, dim3(plan.pool_grid), dim3(DAD_POOL_THREADS), 0, stream, pa);
-    DAD_TRY(hipGetLastError());
+    DAD_RET(launch(plan.pool, plan.pool_grid, stream, pa));
     tk_mark(TK_POOL, stream);
-  } else {
-    pa.ready = pool_ready;   // (zeroed by this step's encoder)
   }
-
-  // 3. losses, DACP mask, analytic backward to dL/de and the classifier grads
-  DadTailArgs ta;
-  memset(&ta, 0, sizeof(ta));
-  ta.cfg = *cfg; ta.yc = bt->yc; ta.logits = st->logits; ta.emb = st->emb; ta.student = st->student;
-  if (explicit_rng) { ta.keep1 = bt->keep1; ta.keep2 = bt->keep2; }
-  ta.key_drop1 = k.drop1; ta.key_drop2 = k.drop2;
-  ta.dacp = st->dacp; ta.tailf = st->tail; ta.ge = ge; ta.ge_ecda = ge_ecda; ta.grad = st->grad;
-  ta.gzb = gzb; ta.eflag = eflag;
-  // 4. ECDA (class-aware MMD + compactness + repulsion) and its embedding grads: after the
-  //    warm-up, in the same launch as the tail (block 0 = tail, blocks 1..C = classes)
-  DadEcdaArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.cfg = *cfg; ca.yc = bt->yc; ca.emb = st->emb; ca.tailf = st->tail;
-  ca.tail_terms = st->tail + DAD_T_ECDA_TERM; ca.ge = ge_ecda; ca.scratch = ecda_scratch; ca.eflag = eflag;
-  ca.sink = ws_ptr<float>(workspace, L.gflat);
-  // the next batch's rows this step prepares: pp in the tail launch, pcw (its clean rows) in the
+  // the next batch's rows this step prepares: in the tail launch, and (its clean rows) in the
   // weight-gradient launch; x16 = NULL: nothing
-  DadPrepArgs pp, pcw;
-  memset(&pp, 0, sizeof(pp));
-  memset(&pcw, 0, sizeof(pcw));
+  DadPrepArgs in_tail, in_wgrad;
+  memset(&in_tail, 0, sizeof(in_tail));
+  memset(&in_wgrad, 0, sizeof(in_wgrad));
   if (plan.prepped) {
-    const DadPrepArgs next = prep_args(ncfg, nbt, ws_ptr<uint16_t>(workspace, L.xs16 + (ncfg->counter & 1u) * L.x16set));
-    if (plan.wgrad_clean) pcw = next;
-    if (plan.tail_prep) { pp = next; prep_only(pp, plan.tail_prep); }
+    const DadPrepArgs next = prep_args(ahead.cfg, ahead.batch, s.ws.set_of(ahead.cfg));
+    if (plan.wgrad_clean) in_wgrad = next;
+    if (plan.tail_prep) { in_tail = next; prep_only(in_tail, plan.tail_prep); }
   }
-  const dim3 tgrid(plan.tail_grid), tblock(DAD_TAIL_THREADS);
-  switch (plan.tail) {
-    case K_TAIL: hipLaunchKernelGGL(dad_tail, tgrid, tblock, 0, stream, ta); break;
-    case K_TAIL_ECDA: hipLaunchKernelGGL(dad_tail_ecda, tgrid, tblock, 0, stream, ta, ca); break;
-    default:   // (the `_s16` sibling when the rows it prepares lie in a 16-bit store, dad_kernels.h)
-      //  a ragged step: its `_rg` sibling, whose pooling sums live slabs only)
-      hipLaunchKernelGGL(cfg->ragged ? dad_tail_ecda_w_rg
-                                     : pp.x16 && dad_prep_s16_needed(pp) ? dad_tail_ecda_w_s16 : dad_tail_ecda_w,
-                         tgrid, tblock, 0, stream, ta, ca, pp, pa);
-      break;
-  }
-  DAD_TRY(hipGetLastError());
+  DAD_RET(launch_tail(s, stream, in_tail, pa));
   tk_mark(TK_TAIL, stream);
-
-  // 5. dW1 as one direct split-K GEMM (G = ReLU' * dL/de / len rebuilt from the tail's dL/dz
-  //    and the ECDA rows), then the split sums with db1, dW2, loss totals, squared-norm partials
-  DadWgradArgs wa;
-  memset(&wa, 0, sizeof(wa));
-  wa.g = G; wa.warmup = cfg->warmup;
-  wa.mask_len = cfg->mask_len; wa.start_hi = cfg->start_hi;
-  wa.xc = static_cast<const float*>(bt->xc); wa.xn = static_cast<const float*>(bt->xn); wa.src = src;   // (FP32 only)
-  if (explicit_rng) { wa.ns = bt->ns; wa.u = bt->u; wa.start = bt->start; }
-  wa.key_strong = k.strong; wa.key_feat = k.feat; wa.key_tstart = k.tstart;
-  wa.strong_std = cfg->strong_std; wa.feat_p = cfg->feat_p;
-  wa.bits = bits; wa.ge = ge; wa.vlen = vlen; wa.xs16 = xs16;
-  wa.splits = plan.splits; wa.ntiles = plan.wgrad_tiles;
-  wa.wpart = ws_ptr<float>(workspace, L.wpart);
-  DadReduceArgs ra;
-  memset(&ra, 0, sizeof(ra));
-  ra.g = G; ra.warmup = cfg->warmup;
-  ra.want_norm = cfg->dp_world == 1;
-  ra.w_kl = cfg->w_kl; ra.w_ecda = cfg->w_ecda;
-  ra.ge_ecda = ge_ecda;
-  ra.gzb = gzb; ra.eflag = eflag; ra.student = st->student; ra.emb = st->emb;
-  if (explicit_rng) { ra.keep1 = bt->keep1; ra.keep2 = bt->keep2; }
-  ra.key_drop1 = k.drop1; ra.key_drop2 = k.drop2; ra.p_drop = cfg->p_drop; ra.drop_scale = cfg->drop_scale;
-  ra.ge = ge; ra.vlen = vlen; ra.cnt_tot = cnt_tot; ra.tailf = st->tail;
-  ra.grad = st->grad; ra.normpart = normpart;
-  ra.pool_abort = plan.pool_grid ? nullptr : pool_ready + DAD_POOL_ABORT;
-  ra.splits = plan.splits; ra.wpart = wa.wpart;
-  const WgradLaunch& wg = kWgradLaunch[plan.wgrad - K_WGRAD_F32];
-  if (cfg->ragged) {
-    const WgradLaunch& rg = kWgradLaunchRg[cfg->precision == DAD_PREC_FP16];
-    if (plan.wgrad_clean) hipLaunchKernelGGL(rg.cp, dim3(plan.wgrad_grid), dim3(rg.threads), 0, stream, wa, ra, pcw);
-    else hipLaunchKernelGGL(rg.kernel, dim3(plan.wgrad_grid), dim3(rg.threads), 0, stream, wa, ra);
-  } else if (wg.cp) {
-    auto cp = wg.cp;
-    if (plan.wgrad_store && pcw.xc_type() != DAD_STORE_F32)
-      cp = cfg->precision == DAD_PREC_FP16 ? dad_wgrad_direct_f16_cps_s16 : dad_wgrad_direct_cps_s16;
-    hipLaunchKernelGGL(cp, dim3(plan.wgrad_grid), dim3(wg.threads), 0, stream, wa, ra, pcw);
-  }
-  else hipLaunchKernelGGL(wg.kernel, dim3(plan.wgrad_grid), dim3(wg.threads), 0, stream, wa, ra);
-  DAD_TRY(hipGetLastError());
+  const DadReduceArgs ra = reduce_args(s);
+  DAD_RET(launch_wgrad(s, stream, in_wgrad, ra));
   tk_mark(TK_WGRAD, stream);
-  const ReduceLaunch& red = kReduceLaunch[plan.reduce - K_REDUCE];
-  hipLaunchKernelGGL(red.kernel, dim3(plan.reduce_grid), dim3(red.threads), 0, stream, ra);
-  DAD_TRY(hipGetLastError());
+  DAD_RET(launch(plan.reduce, plan.reduce_grid, stream, ra));
   tk_mark(TK_RED, stream);
   return DAD_OK;
 }
@@ -402,15 +421,15 @@ int dad_step_backward(const dad_config* cfg, const dad_batch* bt, const dad_stat
 
 int dad_step_backward_ahead(const dad_config* cfg, const dad_batch* bt, const dad_state* st, void* workspace,
                             void* stream, const dad_config* next_cfg, const dad_batch* next_batch, int* prepped) {
-  return step_compute_phases(cfg, bt, st, workspace, stream, false, true, next_cfg, next_batch, prepped);
+  return step_compute_phases(cfg, bt, st, workspace, stream, false, true, Ahead{next_cfg, next_batch, 0, prepped, nullptr});
 }
 
 int dad_step_backward_ahead_split(const dad_config* cfg, const dad_batch* bt, const dad_state* st, void* workspace,
                                   void* stream, const dad_config* next_cfg, const dad_batch* next_batch, int defer,
                                   int* prepped, int* pending) {
   if (!pending || (defer & ~(DAD_PREP_CLEAN | DAD_PREP_NOISY)) != 0) return DAD_E_ARG;
-  return step_compute_phases(cfg, bt, st, workspace, stream, false, true, next_cfg, next_batch, prepped, defer,
-                             pending);
+  return step_compute_phases(cfg, bt, st, workspace, stream, false, true,
+                             Ahead{next_cfg, next_batch, defer, prepped, pending});
 }
 
 int dad_step_prepare_rows(const dad_config* cfg, const dad_batch* bt, void* workspace, void* stream, int parts) {
@@ -432,7 +451,7 @@ int dad_step_prepare_rows(const dad_config* cfg, const dad_batch* bt, void* work
   const DadWs L = dad_ws_layout(geom_of(cfg), max_splits_of(cfg), cfg->precision);
   DadPrepArgs p = prep_args(cfg, bt, ws_ptr<uint16_t>(workspace, L.xs16 + (cfg->counter & 1u) * L.x16set));
   prep_only(p, parts);
-  return launch_prep(p, (hipStream_t)stream, cfg->ragged != 0);
+  return launch_prep(prep_kernel(cfg->ragged != 0, rows_need_s16(cfg, bt, parts)), p, (hipStream_t)stream);
 }
 
 int dad_step_apply(const dad_config* cfg, const dad_state* st, void* workspace, void* stream_) {

@@ -195,13 +195,9 @@ __global__ void dad_encode_wp_f16(DadEncodeArgs a);            // fp16 operands 
 __global__ void dad_prep(DadPrepArgs a);                       // one prepared set, standalone
 // The `_s16` siblings (dad_prep_s16, dad_tail_ecda_w_s16, dad_wgrad_direct[_f16]_cps_s16): the same kernels
 // with the row loads in an fp16 / bf16 store's type, launched in their place when the rows a launch
-// prepares come from such a store (dad_prep_s16_needed).  The step plan names the f32 kernel for both.
+// prepares come from such a store (step_plan.h rows_need_s16).  The step plan resolves the sibling, and
+// dad_step_plan_info reports its family, the f32 kernel.
 __global__ void dad_prep_s16(DadPrepArgs a);
-// a part of p's set that p prepares is read from a 16-bit store
-static inline bool dad_prep_s16_needed(const DadPrepArgs& p) {
-  const bool noisy = !p.warmup && p.g.Bn > 0;
-  return (p.clean && p.xc_type() != DAD_STORE_F32) || (noisy && p.xn_type() != DAD_STORE_F32);
-}
 __global__ void dad_pool(DadPoolArgs a);
 __global__ void dad_tail(DadTailArgs a);
 __global__ void dad_ecda(DadEcdaArgs a);
@@ -222,7 +218,8 @@ __global__ void dad_wgrad_direct_f16_cps(DadWgradArgs a, DadReduceArgs r, DadPre
 __global__ void dad_wgrad_direct_cps_s16(DadWgradArgs a, DadReduceArgs r, DadPrepArgs pc);
 __global__ void dad_wgrad_direct_f16_cps_s16(DadWgradArgs a, DadReduceArgs r, DadPrepArgs pc);
 // The `_rg` siblings: the kernels of a ragged step (dad_config.ragged: FP16 / BF16, both batches store
-// batches), launched in place of the kernels the step plan names, with the same grids.  They read the
+// batches), with the dense kernels' grids; the step plan resolves them too, and dad_step_plan_info reports
+// the dense kernel each stands in for.  They read the
 // batch's lengths on the device and touch live slabs only (dad_common.h, "Ragged mode"); kernels and units
 // of their own, so that the dense kernels compile to what they did without the mode.  The row loads take
 // the store's type at run time (f32, fp16 or bf16: one sibling stands for the f32 kernel and its `_s16` form).

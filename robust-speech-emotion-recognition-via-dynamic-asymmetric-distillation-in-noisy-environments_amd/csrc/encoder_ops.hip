@@ -120,28 +120,21 @@ int encoder_forward_impl(const float* x, const uint8_t* pad, int B, int T, const
   ea.part_sum = ws_ptr<float>(workspace, L.part_sum);
   ea.part_cnt = ws_ptr<float>(workspace, L.part_cnt);
   ea.bits = ws_ptr<uint32_t>(workspace, L.bits);
-  const dim3 egrid((B * G.ncc + 3) / 4);
+  int grid = (B * G.ncc + 3) / 4;
   if (dad_prec16(precision)) {
-    // the rows of x prepared (16-bit conversion: a clean-only set), then the GEMM on them
+    // the rows of x prepared (16-bit conversion: a clean-only set of a padded f32 batch), then the GEMM on them
     DadPrepArgs pp;
     memset(&pp, 0, sizeof(pp));
     pp.g = G; pp.warmup = 1; pp.clean = 1; pp.f16 = f16 ? 1 : 0; pp.xc = x;
     pp.x16 = ws_ptr<uint16_t>(workspace, L.xs16);
-    const int rp = launch_prep(pp, stream);
-    if (rp) return rp;
+    DAD_RET(launch_prep(prep_kernel(false, false), pp, stream));
     ea.x16c = pp.x16;
     int cus = 0;
-    const int rc = device_cus(&cus);
-    if (rc) return rc;
-    const int rs = wp_split(G, 0, cus, ea.ws_nt, ea.ws_ns);
-    if (rs) return rs;
-    const dim3 grid(ea.ws_nt + ea.ws_ns);
-    if (f16) hipLaunchKernelGGL(dad_encode_wp_f16, grid, dim3(DAD_ENC_WS_THREADS), 0, stream, ea);
-    else hipLaunchKernelGGL(dad_encode_wp, grid, dim3(DAD_ENC_WS_THREADS), 0, stream, ea);
-  } else {
-    hipLaunchKernelGGL(dad_encode_f32, egrid, dim3(DAD_ENC_F32_THREADS), 0, stream, ea);
+    DAD_RET(device_cus(&cus));
+    DAD_RET(wp_split(G, 0, cus, ea.ws_nt, ea.ws_ns));
+    grid = ea.ws_nt + ea.ws_ns;
   }
-  DAD_TRY(hipGetLastError());
+  DAD_RET(launch(encode_kernel(precision, false), grid, stream, ea));
   if (e_out) {
     hipLaunchKernelGGL(dad_embed_kernel, dim3(B), dim3(256), 0, stream, ea.part_sum, pad, B, T, G.ncc, vlen_out,
                        e_out);
@@ -203,16 +196,14 @@ int dad_encoder_backward(const float* x, const uint8_t* pad, int B, int T, const
   wa.wpart = ws_ptr<float>(workspace, L.wpart);
   DadReduceArgs none;
   memset(&none, 0, sizeof(none));
-  hipLaunchKernelGGL(dad_wgrad_f32, dim3(6 * splits), dim3(DAD_WGRAD_THREADS), 0, stream, wa, none);
-  DAD_TRY(hipGetLastError());
+  DAD_RET(launch(K_WGRAD_F32, 6 * splits, stream, wa, none));
   float* gflat = ws_ptr<float>(workspace, L.gflat);
   DadReduceArgs ra;
   memset(&ra, 0, sizeof(ra));
   ra.g = G; ra.splits = splits; ra.warmup = 1; ra.want_norm = 0;
   ra.wpart = wa.wpart; ra.ge = de; ra.vlen = vlen; ra.cnt_tot = cnt_tot;
   ra.tailf = nullptr; ra.grad = gflat; ra.normpart = ws_ptr<float>(workspace, L.normpart);
-  hipLaunchKernelGGL(dad_reduce, dim3(DAD_REDUCE_BLOCKS), dim3(DAD_REDUCE_THREADS), 0, stream, ra);
-  DAD_TRY(hipGetLastError());
+  DAD_RET(launch(K_REDUCE, DAD_REDUCE_BLOCKS, stream, ra));
   DAD_TRY(hipMemcpyAsync(dw1, gflat + DAD_OFF_W1, sizeof(float) * DAD_H * DAD_D, hipMemcpyDeviceToDevice, stream));
   DAD_TRY(hipMemcpyAsync(db1, gflat + DAD_OFF_B1, sizeof(float) * DAD_H, hipMemcpyDeviceToDevice, stream));
   return DAD_OK;

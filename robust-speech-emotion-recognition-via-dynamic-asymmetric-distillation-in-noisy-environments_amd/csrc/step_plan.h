@@ -1,7 +1,8 @@
-// The host plan of one DAD step: which kernels its launches are and how large their grids, decided
-// in one place (plan_step) from the configs and the presence of batch pointers.  Host code only:
-// no HIP call, no allocation, nothing read through a batch pointer.  The step's enqueue code
-// (dad_abi.hip) launches what the plan says; dad_step_plan (dad.h) shows the same plan to tests.
+// The host plan of one DAD step: which entry point each of its launches is (the `_s16` / `_rg` siblings
+// included) and how large its grid, decided in one place (plan_step) from the configs and the batch
+// structs' own fields (which pointers are present, the store row types).  Host code only: no HIP call,
+// no allocation, nothing read through a batch pointer.  The step's enqueue code (dad_abi.hip) launches
+// what the plan says; dad_step_plan and dad_step_plan_kernels (dad.h) show the same plan to tests.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -117,31 +118,90 @@ inline int wp_split(const DadGeom& G, int Bn, int cus, int& nt, int& ns) {
 // standalone dad_prep: ~4 workgroups of 4 waves per CU, two rows in flight per wave
 inline int prep_grid_of(int cus) { return 4 * cus; }
 
-// The kernels a step launches;kStepKernelName spells them as the profile tools do.
-enum StepKernel {
-  K_ENCODE_F32, K_ENCODE_WP, K_ENCODE_WP_F16,
-  K_TAIL, K_TAIL_ECDA, K_TAIL_ECDA_W,
-  K_WGRAD_F32, K_WGRAD_DIRECT, K_WGRAD_DIRECT_CP, K_WGRAD_DIRECT_CPS,
-  K_WGRAD_DIRECT_F16, K_WGRAD_DIRECT_F16_CP, K_WGRAD_DIRECT_F16_CPS,
-  K_REDUCE, K_REDUCE_W, K_COUNT
-};
-constexpr const char* kStepKernelName[K_COUNT] = {
-    "dad_encode_f32", "dad_encode_wp", "dad_encode_wp_f16",
-    "dad_tail", "dad_tail_ecda", "dad_tail_ecda_w",
-    "dad_wgrad_f32", "dad_wgrad_direct", "dad_wgrad_direct_cp", "dad_wgrad_direct_cps",
-    "dad_wgrad_direct_f16", "dad_wgrad_direct_f16_cp", "dad_wgrad_direct_f16_cps",
-    "dad_reduce", "dad_reduce_w"};
+// Every entry point a step can launch, once: X(id, entry point, family, argument blocks, block size).  The
+// StepKernel enum and kStepKernels below and the launch table (dad_host.h) are all expansions of this
+// list, so none of them can fall out of step with another.  The name is the entry point's, spelt as the
+// profile tools do.  The family is the kernel dad_step_plan_info reports for it: a base kernel its own,
+// an `_s16` / `_rg` sibling (dad_kernels.h) the kernel it stands in for.  The argument blocks (KernelSig)
+// say which launch helper takes it.
+#define DAD_STEP_KERNELS(X)                                                                              \
+  X(K_PREP, dad_prep, K_PREP, SIG_PREP, DAD_PREP_THREADS)                                                \
+  X(K_PREP_S16, dad_prep_s16, K_PREP, SIG_PREP, DAD_PREP_THREADS)                                        \
+  X(K_PREP_RG, dad_prep_rg, K_PREP, SIG_PREP, DAD_PREP_THREADS)                                          \
+  X(K_ENCODE_F32, dad_encode_f32, K_ENCODE_F32, SIG_ENCODE, DAD_ENC_F32_THREADS)                         \
+  X(K_ENCODE_WP, dad_encode_wp, K_ENCODE_WP, SIG_ENCODE, DAD_ENC_WS_THREADS)                             \
+  X(K_ENCODE_WP_F16, dad_encode_wp_f16, K_ENCODE_WP_F16, SIG_ENCODE, DAD_ENC_WS_THREADS)                 \
+  X(K_ENCODE_WP_RG, dad_encode_wp_rg, K_ENCODE_WP, SIG_ENCODE, DAD_ENC_WS_THREADS)                       \
+  X(K_ENCODE_WP_F16_RG, dad_encode_wp_f16_rg, K_ENCODE_WP_F16, SIG_ENCODE, DAD_ENC_WS_THREADS)           \
+  X(K_POOL, dad_pool, K_POOL, SIG_POOL, DAD_POOL_THREADS)                                                \
+  X(K_POOL_RG, dad_pool_rg, K_POOL, SIG_POOL, DAD_POOL_THREADS)                                          \
+  X(K_TAIL, dad_tail, K_TAIL, SIG_TAIL, DAD_TAIL_THREADS)                                                \
+  X(K_TAIL_ECDA, dad_tail_ecda, K_TAIL_ECDA, SIG_TAIL_ECDA, DAD_TAIL_THREADS)                            \
+  X(K_TAIL_ECDA_W, dad_tail_ecda_w, K_TAIL_ECDA_W, SIG_TAIL_W, DAD_TAIL_THREADS)                         \
+  X(K_TAIL_ECDA_W_S16, dad_tail_ecda_w_s16, K_TAIL_ECDA_W, SIG_TAIL_W, DAD_TAIL_THREADS)                 \
+  X(K_TAIL_ECDA_W_RG, dad_tail_ecda_w_rg, K_TAIL_ECDA_W, SIG_TAIL_W, DAD_TAIL_THREADS)                   \
+  X(K_WGRAD_F32, dad_wgrad_f32, K_WGRAD_F32, SIG_WGRAD, DAD_WGRAD_THREADS)                               \
+  X(K_WGRAD_DIRECT, dad_wgrad_direct, K_WGRAD_DIRECT, SIG_WGRAD, WGD_THREADS)                            \
+  X(K_WGRAD_DIRECT_CP, dad_wgrad_direct_cp, K_WGRAD_DIRECT_CP, SIG_WGRAD_CP, WGD_THREADS)                \
+  X(K_WGRAD_DIRECT_CPS, dad_wgrad_direct_cps, K_WGRAD_DIRECT_CPS, SIG_WGRAD_CP, WGD_THREADS)             \
+  X(K_WGRAD_DIRECT_F16, dad_wgrad_direct_f16, K_WGRAD_DIRECT_F16, SIG_WGRAD, WGD_THREADS)                \
+  X(K_WGRAD_DIRECT_F16_CP, dad_wgrad_direct_f16_cp, K_WGRAD_DIRECT_F16_CP, SIG_WGRAD_CP, WGD_THREADS)    \
+  X(K_WGRAD_DIRECT_F16_CPS, dad_wgrad_direct_f16_cps, K_WGRAD_DIRECT_F16_CPS, SIG_WGRAD_CP, WGD_THREADS) \
+  X(K_WGRAD_DIRECT_CPS_S16, dad_wgrad_direct_cps_s16, K_WGRAD_DIRECT_CPS, SIG_WGRAD_CP, WGD_THREADS)     \
+  X(K_WGRAD_DIRECT_F16_CPS_S16, dad_wgrad_direct_f16_cps_s16, K_WGRAD_DIRECT_F16_CPS, SIG_WGRAD_CP, WGD_THREADS) \
+  X(K_WGRAD_DIRECT_RG, dad_wgrad_direct_rg, K_WGRAD_DIRECT, SIG_WGRAD, WGD_THREADS)                      \
+  X(K_WGRAD_DIRECT_F16_RG, dad_wgrad_direct_f16_rg, K_WGRAD_DIRECT_F16, SIG_WGRAD, WGD_THREADS)          \
+  X(K_WGRAD_DIRECT_CPS_RG, dad_wgrad_direct_cps_rg, K_WGRAD_DIRECT_CPS, SIG_WGRAD_CP, WGD_THREADS)       \
+  X(K_WGRAD_DIRECT_F16_CPS_RG, dad_wgrad_direct_f16_cps_rg, K_WGRAD_DIRECT_F16_CPS, SIG_WGRAD_CP, WGD_THREADS) \
+  X(K_REDUCE, dad_reduce, K_REDUCE, SIG_REDUCE, DAD_REDUCE_THREADS)                                      \
+  X(K_REDUCE_W, dad_reduce_w, K_REDUCE_W, SIG_REDUCE, 64)
+
+#define DAD_X_ID(id, fn, family, sig, threads) id,
+enum StepKernel { DAD_STEP_KERNELS(DAD_X_ID) K_COUNT };
+#undef DAD_X_ID
+// the argument blocks an entry point takes (dad_host.h SigOf spells each list out)
+enum KernelSig { SIG_PREP, SIG_ENCODE, SIG_POOL, SIG_TAIL, SIG_TAIL_ECDA, SIG_TAIL_W, SIG_WGRAD, SIG_WGRAD_CP, SIG_REDUCE };
+struct StepKernelInfo { const char* name; StepKernel family; KernelSig sig; int threads; };
+#define DAD_X_INFO(id, fn, family, sig, threads) {#fn, family, sig, threads},
+constexpr StepKernelInfo kStepKernels[K_COUNT] = {DAD_STEP_KERNELS(DAD_X_INFO)};
+#undef DAD_X_INFO
+inline const char* family_name(StepKernel k) { return kStepKernels[kStepKernels[k].family].name; }
+
+// Kernel selection, shared by plan_step, dad_step_prepare_rows and the modular encoder ops.
+// Rows that a launch prepares (DAD_PREP_* parts of (cfg, batch)'s set) lie in a 16-bit store, so the
+// launch is the `_s16` form; batch NULL: a padded f32 batch.  Reads the struct's own fields only.
+inline bool rows_need_s16(const dad_config* cfg, const dad_batch* batch, int parts) {
+  if (!batch) return false;
+  return ((parts & DAD_PREP_CLEAN) && batch->xc_dtype != DAD_STORE_F32) ||
+         ((parts & DAD_PREP_NOISY) && !cfg->warmup && cfg->Bn > 0 && batch->xn_dtype != DAD_STORE_F32);
+}
+// the standalone preparation: the ragged sibling reads any store type, hence before the `_s16` one
+inline StepKernel prep_kernel(bool ragged, bool s16) { return ragged ? K_PREP_RG : s16 ? K_PREP_S16 : K_PREP; }
+inline StepKernel encode_kernel(int precision, bool ragged) {
+  if (!dad_prec16(precision)) return K_ENCODE_F32;
+  const bool f16 = precision == DAD_PREC_FP16;
+  if (ragged) return f16 ? K_ENCODE_WP_F16_RG : K_ENCODE_WP_RG;
+  return f16 ? K_ENCODE_WP_F16 : K_ENCODE_WP;
+}
 // the 16-bit weight gradient by [fp16][takes the next batch's clean rows][through its store table]
 constexpr StepKernel kWgradDirect[2][2][2] = {
     {{K_WGRAD_DIRECT, K_WGRAD_DIRECT}, {K_WGRAD_DIRECT_CP, K_WGRAD_DIRECT_CPS}},
     {{K_WGRAD_DIRECT_F16, K_WGRAD_DIRECT_F16}, {K_WGRAD_DIRECT_F16_CP, K_WGRAD_DIRECT_F16_CPS}}};
+// ... a ragged step's by [fp16][takes the (ragged, store) next batch's clean rows], and the `_cps`
+// kernel's sibling for clean rows in a 16-bit store by [fp16]
+constexpr StepKernel kWgradDirectRg[2][2] = {{K_WGRAD_DIRECT_RG, K_WGRAD_DIRECT_CPS_RG},
+                                             {K_WGRAD_DIRECT_F16_RG, K_WGRAD_DIRECT_F16_CPS_RG}};
+constexpr StepKernel kWgradDirectCpsS16[2] = {K_WGRAD_DIRECT_CPS_S16, K_WGRAD_DIRECT_F16_CPS_S16};
 
+// The launches of a step in their order: the exact entry point of each, and its grid (0: not made).
 struct StepPlan {
   int splits, max_splits;       // this step's split-K factor; the one its workspace is laid out for
+  StepKernel prep;
   int prep_grid;                // standalone dad_prep of this step's rows before the encoder (all parts); 0: none
   StepKernel encode;
   int encode_grid, ws_nt, ws_ns;   // (ws_nt / ws_ns: dad_encode_wp's roles; encode_rc: wp_split's code)
   int encode_rc;
+  StepKernel pool;
   int pool_grid;                // the separate dad_pool; 0: the tail launch pools
   StepKernel tail;
   int tail_grid;
@@ -177,35 +237,38 @@ inline bool can_prepare_ahead(const dad_config* cfg, int max_splits, const dad_c
 // cfg: a config check_cfg accepts.  (next_cfg, next_batch): the step after it, or NULL; one that does
 // not qualify (can_prepare_ahead) is prepared by its own step.  defer: the DAD_PREP_* parts of the
 // next batch's rows this step's launches leave to the caller (dad_step_prepare_rows).  cus: the
-// device's compute units.
-inline StepPlan plan_step(const dad_config* cfg, const dad_config* next_cfg, const dad_batch* next_batch, int defer,
-                          int cus) {
+// device's compute units.  batch: this step's, or NULL for a padded f32 one; of it and of next_batch
+// only the struct's own fields are read (NULL-ness of pointers, xc_dtype / xn_dtype).
+inline StepPlan plan_step(const dad_config* cfg, const dad_batch* batch, const dad_config* next_cfg,
+                          const dad_batch* next_batch, int defer, int cus) {
   StepPlan p = {};
   const DadGeom G = geom_of(cfg);
   const int Bn = cfg->warmup ? 0 : G.Bn;
-  const bool h16 = dad_prec16(cfg->precision), f16 = cfg->precision == DAD_PREC_FP16;
+  const bool h16 = dad_prec16(cfg->precision), f16 = cfg->precision == DAD_PREC_FP16, ragged = cfg->ragged != 0;
   p.splits = splits_of(cfg);
   p.max_splits = max_splits_of(cfg);
 
   // encoder.  16-bit: augmentation + conversion (unless the previous step prepared this batch),
   // then the W-stationary GEMM on the prepared set.  FP32: one wave per 32-row slab, four per
   // workgroup.
+  p.prep = prep_kernel(ragged, rows_need_s16(cfg, batch, DAD_PREP_CLEAN | DAD_PREP_NOISY));
+  p.encode = encode_kernel(cfg->precision, ragged);
   if (h16) {
     if (!cfg->prepped) p.prep_grid = prep_grid_of(cus);
     p.encode_rc = wp_split(G, Bn, cus, p.ws_nt, p.ws_ns);
-    p.encode = f16 ? K_ENCODE_WP_F16 : K_ENCODE_WP;
     p.encode_grid = p.ws_nt + p.ws_ns;
   } else {
-    p.encode = K_ENCODE_F32;
     p.encode_grid = (G.Bc * G.ncc + Bn * G.ncn + 3) / 4;
   }
 
   // pooling and tail.  Batches of at most 64 utterances per side with class-aware MMD, after the
   // warm-up: the wave-centric launch, whose spare blocks pool the embeddings (one item per wave,
   // Bc + 2 Bn items) instead of a separate dad_pool launch.  Warm-up: no ECDA.  Otherwise block 0 is
-  // the tail and blocks 1..C the classes.
+  // the tail and blocks 1..C the classes.  (A ragged step pools live slabs only, in dad_pool_rg or in
+  // dad_tail_ecda_w_rg; dad_tail and dad_tail_ecda do not pool and have no sibling.)
   const bool tail_w = !cfg->warmup && G.Bc <= 64 && Bn <= 64 && cfg->class_aware && tail_w_on();
   const int items = G.Bc + 2 * Bn, waves = DAD_TAIL_THREADS / 64;
+  p.pool = ragged ? K_POOL_RG : K_POOL;
   if (!tail_w) p.pool_grid = items;
   p.tail = cfg->warmup ? K_TAIL : tail_w ? K_TAIL_ECDA_W : K_TAIL_ECDA;
   p.tail_grid = cfg->warmup ? 1 : 1 + DAD_C + (tail_w ? (items + waves - 1) / waves : 0);
@@ -220,12 +283,17 @@ inline StepPlan plan_step(const dad_config* cfg, const dad_config* next_cfg, con
     p.tail_prep = (defer & DAD_PREP_NOISY) ? 0 : DAD_PREP_NOISY;
     if (p.tail_prep) p.tail_grid = std::max(p.tail_grid, std::max(cus, 2 * (1 + DAD_C)));
   }
+  // (the `_s16` tail: when the rows it prepares lie in a 16-bit store)
+  if (tail_w && ragged) p.tail = K_TAIL_ECDA_W_RG;
+  else if (p.tail_prep && rows_need_s16(next_cfg, next_batch, p.tail_prep)) p.tail = K_TAIL_ECDA_W_S16;
 
   // weight gradient and the split sums.  16-bit: WGD_NDB column blocks per split, the grid a
   // multiple of 8 (XCD-aware tile order) with WGD_XWG spare workgroups for the reduce's extra blocks.
   // FP32: one tile = (split, 128 columns); then every reduce block.
   if (h16) {
-    p.wgrad = kWgradDirect[f16][p.wgrad_clean][p.wgrad_store];
+    if (ragged) p.wgrad = kWgradDirectRg[f16][p.wgrad_clean];
+    else if (p.wgrad_store && next_batch->xc_dtype != DAD_STORE_F32) p.wgrad = kWgradDirectCpsS16[f16];
+    else p.wgrad = kWgradDirect[f16][p.wgrad_clean][p.wgrad_store];
     p.wgrad_tiles = WGD_NDB * p.splits;
     p.wgrad_grid = (p.wgrad_tiles + WGD_XWG + 7) / 8 * 8;
     p.reduce = K_REDUCE_W;

@@ -149,6 +149,132 @@ def test_error_returns():
     assert L.dad_step_plan(c, ncfg, None, 0, 256, ctypes.byref(info)) == 0 and info.prepped == 0
 
 
+# ---- the exact entry points (dad_step_plan_kernels): the `_s16` / `_rg` siblings the plan resolves, which
+# dad_step_plan_info reports under their family names.  A wrong sibling reads rows with the wrong element size
+# on a GPU; here it is a wrong string.
+LAUNCHES = ("prep", "encode", "pool", "tail", "wgrad", "reduce")
+EXACT = dict(prep="dad_prep", encode="dad_encode_wp_f16", pool=None, tail="dad_tail_ecda_w",
+             wgrad="dad_wgrad_direct_f16", reduce="dad_reduce_w")                          # the bench step again
+EXACT_RG = dict(prep="dad_prep_rg", encode="dad_encode_wp_f16_rg", pool=None, tail="dad_tail_ecda_w_rg",
+                wgrad="dad_wgrad_direct_f16_rg", reduce="dad_reduce_w")
+F32, F16, BF16 = 0, 1, 2
+SMALL = dict(B=5, T=37, Bn=3, Tn=41)
+
+
+def _batch(store=False, xc=F32, xn=F32):
+    """This step's batch: made-up addresses, as _next's."""
+    nbt = _next(_cfg(), store=store)[1]
+    nbt.xc_dtype, nbt.xn_dtype = xc, xn
+    return nbt
+
+
+def _next16(cfg, xc, xn, **kw):
+    ncfg, nbt = _next(cfg, store=True, **kw)
+    nbt.xc_dtype, nbt.xn_dtype = xc, xn
+    return ncfg, nbt
+
+
+def _ragged(**kw):
+    c = _cfg(**kw)
+    c.ragged = 1
+    return c
+
+
+def _family(name):
+    for suffix in ("_s16", "_rg"):
+        if name.endswith(suffix):
+            return name[:-len(suffix)]
+    return name
+
+
+def _kernels(cfg, batch=None, nxt=(None, None), defer=0, cus=256):
+    lib = dadpkg.pkg()._lib
+    out = (ctypes.c_char_p * lib.STEP_LAUNCHES)()
+    assert lib.lib().dad_step_plan_kernels(cfg, batch, nxt[0], nxt[1], defer, cus, out) == 0
+    got = {k: (v.decode() if v is not None else None) for k, v in zip(LAUNCHES, out)}
+    # every name is its dad_step_plan_info string's sibling, and NULL exactly where the info's grid is 0
+    info = _plan(cfg, nxt, defer, cus)
+    info.update(prep="dad_prep", pool="dad_pool")
+    for k, name in got.items():
+        assert (name is None) == (info[k + "_grid"] == 0), (k, name, info[k + "_grid"])
+        assert name is None or _family(name) == info[k], (k, name, info[k])
+    return got
+
+
+def test_exact_kernels_of_this_steps_own_launches():
+    c = _cfg()
+    assert _kernels(c) == EXACT                                               # 1
+    p = _cfg()
+    p.prepped = 1
+    assert _kernels(p) == dict(EXACT, prep=None)                              # 2
+    assert _kernels(c, _batch(store=True)) == EXACT                           # 3: an f32 store
+    for shape in (dict(), SMALL):                                             # 4: a part of the set in a 16-bit store
+        c = _cfg(**shape)
+        for xc, xn in ((F16, F16), (BF16, F32), (F32, BF16)):
+            assert _kernels(c, _batch(True, xc, xn)) == dict(EXACT, prep="dad_prep_s16"), (shape, xc, xn)
+    c = _cfg(precision="fp32")                                                # 18
+    assert _kernels(c) == dict(prep=None, encode="dad_encode_f32", pool=None, tail="dad_tail_ecda_w",
+                               wgrad="dad_wgrad_f32", reduce="dad_reduce")
+    c = _cfg(64, 300, 0, 0, epoch=0)                                          # 19: dense warm-up
+    assert _kernels(c) == dict(EXACT, pool="dad_pool", tail="dad_tail")
+
+
+def test_exact_kernels_that_prepare_the_next_batch():
+    c = _cfg()
+    assert _kernels(c, None, _next(c)) == dict(EXACT, wgrad="dad_wgrad_direct_f16_cp")                     # 5
+    assert _kernels(c, None, _next(c, store=True)) == dict(EXACT, wgrad="dad_wgrad_direct_f16_cps")        # 6
+    for shape in (dict(), SMALL):
+        c = _cfg(**shape)
+        assert _kernels(c, None, _next16(c, F16, F32)) == dict(EXACT, wgrad="dad_wgrad_direct_f16_cps_s16")   # 7
+        assert _kernels(c, None, _next16(c, F32, BF16)) == dict(EXACT, wgrad="dad_wgrad_direct_f16_cps",      # 8
+                                                                tail="dad_tail_ecda_w_s16")
+    # the deferred part's rows are dad_step_prepare_rows': the launch that no longer reads them is the f32 kernel
+    c = _cfg()
+    nxt = _next16(c, F16, F16)
+    assert _kernels(c, None, nxt, defer=CLEAN) == dict(EXACT, tail="dad_tail_ecda_w_s16")                  # 9
+    assert _kernels(c, None, nxt, defer=NOISY) == dict(EXACT, wgrad="dad_wgrad_direct_f16_cps_s16")        # 10
+    assert _kernels(c, None, nxt, defer=CLEAN | NOISY) == EXACT                                            # 11
+    b = _cfg(precision="bf16")                                                                             # 12
+    assert _kernels(b, None, _next16(b, BF16, BF16)) == dict(EXACT, encode="dad_encode_wp", tail="dad_tail_ecda_w_s16",
+                                                            wgrad="dad_wgrad_direct_cps_s16")
+
+
+def test_exact_kernels_of_ragged_steps():
+    for shape in (dict(), SMALL):
+        assert _kernels(_ragged(**shape), _batch(True, F16, F16)) == EXACT_RG                              # 13
+    c = _ragged()
+    nxt = _next16(c, F16, BF16)
+    assert nxt[0].ragged == 1
+    assert _kernels(c, _batch(True), nxt) == dict(EXACT_RG, wgrad="dad_wgrad_direct_f16_cps_rg")           # 14
+    assert _kernels(c, _batch(True), nxt, defer=CLEAN) == EXACT_RG                                         # 15
+    w = _ragged(B=64, T=300, Bn=0, Tn=0, epoch=0)                                                          # 16: warm-up
+    assert w.warmup == 1
+    assert _kernels(w, _batch(True)) == dict(EXACT_RG, pool="dad_pool_rg", tail="dad_tail")
+    big = _ragged(B=96, T=300, Bn=96, Tn=300)                            # 17: the general tail has no ragged sibling
+    assert _kernels(big, _batch(True)) == dict(EXACT_RG, pool="dad_pool_rg", tail="dad_tail_ecda")
+
+
+def test_exact_kernels_error_returns():
+    lib = dadpkg.pkg()._lib
+    L = lib.lib()
+    out = (ctypes.c_char_p * lib.STEP_LAUNCHES)()
+    c = _cfg()
+    assert L.dad_step_plan_kernels(c, _batch(False, F16, F32), None, None, 0, 256, out) == lib.E_ARG    # padded is f32
+    assert L.dad_step_plan_kernels(_cfg(precision="fp32"), _batch(True, F16, F16), None, None, 0, 256, out) == lib.E_UNSUPPORTED
+    assert L.dad_step_plan_kernels(c, None, None, None, 0, 256, None) == lib.E_ARG
+    assert L.dad_step_plan_kernels(c, None, None, None, 0, 1, out) == lib.E_ARG                         # as dad_step_plan
+    assert L.dad_step_plan_kernels(None, None, None, None, 0, 256, out) == lib.E_ARG
+
+
+def test_tail_w_switch_selects_the_general_tail_of_a_ragged_step():
+    """DAD_TAIL_W=0 in a child (below): row 14's step pools in dad_pool_rg and runs the general tail."""
+    code = ("import test_step_plan_cpu as t; c = t._ragged(); "
+            "g = t._kernels(c, t._batch(True), t._next16(c, t.F16, t.BF16)); print(g['pool'], g['tail'], g['wgrad'])")
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, DAD_TAIL_W="0"),
+                         cwd=os.path.dirname(os.path.abspath(__file__)), check=True, stdout=subprocess.PIPE, text=True)
+    assert out.stdout.split() == ["dad_pool_rg", "dad_tail_ecda", "dad_wgrad_direct_f16_rg"]
+
+
 def test_tail_w_switch_selects_the_general_tail():
     """DAD_TAIL_W=0 (read once per process, hence a child): the bench step pools separately and runs
     the general tail + ECDA launch."""
