@@ -418,7 +418,12 @@ static inline __host__ __device__ int dad_rg_dense_job(const int* ps, int Bc, in
   if (u < Bc) return u * ncc + c;
   return (teacher ? 0 : Bc * ncc) + (u - Bc) * ncn + c;
 }
-// wg_range's formula (wgrad.hip) on a list of `total` slabs: split's contiguous share [s0, s1)
+// slabs of the weight-gradient row list: the clean slabs, then (past warm-up) the strong slabs
+static inline __host__ __device__ int dad_wg_total(const DadGeom& g, int warmup) {
+  return g.Bc * g.ncc + (warmup ? 0 : g.Bn * g.ncn);
+}
+// a split's contiguous share [s0, s1) of a list of `total` slabs, an empty one as s0 = s1 (the ragged step's
+// live list, on the host and in the `_rg` kernels; the dense kernels: wg_range, wgrad_common.h)
 static inline __host__ __device__ void dad_wg_share(int total, int splits, int split, int& s0, int& s1) {
   const int per = (total + splits - 1) / splits;
   s0 = split * per;
@@ -521,7 +526,7 @@ static inline size_t dad_align(size_t x) { return (x + 255) & ~(size_t)255; }
 #endif
 static inline int dad_wgd_min_splits(int total) { return (total + 63) / 64; }
 static inline int dad_auto_splits(const DadGeom& g, int precision, int warmup) {
-  const int total = g.Bc * g.ncc + (warmup ? 0 : g.Bn * g.ncn);
+  const int total = dad_wg_total(g, warmup);
   // FP32: 42 splits x 6 column blocks = 252 tiles, one per CU
   const int target = dad_prec16(precision) ? WGD_SPLITS : 42;
   int s = total < target ? total : target;

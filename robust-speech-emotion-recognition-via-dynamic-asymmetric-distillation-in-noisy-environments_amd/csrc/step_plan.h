@@ -57,8 +57,7 @@ inline int splits_of(const dad_config* c) {
   if (c->splits <= 0) return dad_auto_splits(g, c->precision, c->warmup);
   if (!dad_prec16(c->precision)) return c->splits;
   // dad_wgrad_direct holds at most WGD_MAXU slabs' utterances per split
-  const int total = g.Bc * g.ncc + (c->warmup ? 0 : g.Bn * g.ncn);
-  return std::max(c->splits, dad_wgd_min_splits(total));
+  return std::max(c->splits, dad_wgd_min_splits(dad_wg_total(g, c->warmup)));
 }
 
 inline int max_splits_of(const dad_config* c) {

@@ -1,307 +1,11 @@
-// Encoder weight gradient: dW1 = sum_rows G[row]^T x[row],  G = relu'(pre) * valid * dL/de_b / len_b
-// (autograd of pre_net + ReLU + masked mean pool, I/model.py:28-36, for the clean branch
-// (I/train.py:399) and the strong-augmented noisy branch (I/train.py:439)).
-//
-// K = rows (B*T per branch) is long and the output (256x768) small, so the reduction is
-// split over `splits` row ranges; each workgroup writes one f32 partial slab, and
-// dad_reduce sums them in a fixed order (deterministic, no float atomics).
-// G is rebuilt on the fly from the ReLU' bit mask written by the forward and the
-// per-(utterance, h) scale dL/de / len.  The strong branch's augmented input is
-//   FP32: regenerated exactly (same counter-RNG function, or re-read explicit noise);
-//   FP16/BF16: re-read from the 16-bit copy the forward stored (the exact MFMA operand it used).
-// Both run after the losses as one direct split-K GEMM with the loss scale folded into G.
+// The 16-bit direct weight gradient: the templated body of the dad_wgrad_direct* kernels.  The including unit
+// (wgrad_direct.hip, wgrad_direct_rg.hip) defines the stamp macros WGD_CLK(), WGD_ACC(k, v) and WGD_ZERO() first
+// (whether the stamps build records anything is its choice), then names its kernels with WGD_KERNEL[_CP].
+#pragma once
 #include <type_traits>
 
-#include "dad_common.h"
-#include "dad_kernels.h"
+#include "wgrad_common.h"
 #include "dad_prep.h"
-#include "dad_probe.h"
-
-namespace {
-
-__device__ __forceinline__ int wg_tstart(const DadWgradArgs& a, int b) {
-  if (a.start) return (int)a.start[b];
-  return dad_tstart_at(a.key_tstart, b, a.start_hi);
-}
-
-__device__ __forceinline__ float wg_featkeep(const DadWgradArgs& a, int d) {
-  return dad_feat_keep(a.u, a.key_feat, d, a.feat_p);
-}
-
-// slab s of the weight-gradient row list: clean slabs first, then strong (noisy) slabs
-struct SlabIdx {
-  int br, b, c, T;
-  int erow;          // row of ge / vlen (clean b, or Bc + b)
-  size_t row0;       // [b][T] row of frame 0
-  size_t bits_slab;  // slab index in the ReLU' row-mask buffer (= s)
-};
-__device__ __forceinline__ SlabIdx wg_slab(const DadWgradArgs& a, int s) {
-  const DadGeom& g = a.g;
-  const int nsc = g.Bc * g.ncc;
-  SlabIdx r;
-  r.br = s >= nsc;
-  const int rem = r.br ? s - nsc : s;
-  const int nc = r.br ? g.ncn : g.ncc;
-  r.b = rem / nc;
-  r.c = rem - r.b * nc;
-  r.T = r.br ? g.Tn : g.Tc;
-  r.erow = r.br ? g.Bc + r.b : r.b;
-  r.row0 = (size_t)r.b * r.T;
-  r.bits_slab = (size_t)s;
-  return r;
-}
-
-__device__ __forceinline__ int wg_total(const DadWgradArgs& a) {
-  return a.g.Bc * a.g.ncc + (a.warmup ? 0 : a.g.Bn * a.g.ncn);
-}
-
-// slab range [s0, s1) of a split: a contiguous share of all slabs
-__device__ __forceinline__ void wg_range(const DadWgradArgs& a, int split, int& s0, int& s1) {
-  const int total = wg_total(a);
-  const int per = (total + a.splits - 1) / a.splits;
-  s0 = split * per;
-  s1 = min(total, s0 + per);
-}
-
-// Fused step: dL/de of utterance row u (clean u < Bc, strong Bc + b), hidden unit h: the
-// classifier part keep(u,h) * sum_c W2[c][h] dL/dz[u][c] (nn.Linear + nn.Dropout backward,
-// I/model.py:62-63) plus the ECDA part where ECDA wrote the row.
-// ec = ge_ecda[u][h] as loaded by the caller (read whatever the flag: unflagged rows hold
-// stale values and are selected away, so a caller can keep all its loads in flight)
-// EX: explicit dropout masks (a.keep1 set), chosen by the caller outside its loops
-// (gz = dL/dz[u], ef = eflag[u], ec as loaded by the caller)
-template <bool EX>
-__device__ __forceinline__ float fused_ge1_v(const DadReduceArgs& a, int Bc, int u, int h, const float (&w2)[4],
-                                             const f32x4& gz, uint32_t ef, float ec, float* kv_out = nullptr) {
-  const bool strong = u >= Bc;
-  const int b = strong ? u - Bc : u;
-  const float kv = keep_value_t<EX>(strong ? a.keep2 : a.keep1, strong ? a.key_drop2 : a.key_drop1, b, h, a.p_drop,
-                                    a.drop_scale);
-  if (kv_out) *kv_out = kv;
-  const float z = ((w2[0] * gz[0] + w2[1] * gz[1]) + w2[2] * gz[2]) + w2[3] * gz[3];
-  return z * kv + (ef ? ec : 0.0f);
-}
-template <bool EX>
-__device__ __forceinline__ float fused_ge1_ec(const DadReduceArgs& a, int Bc, int u, int h, const float (&w2)[4],
-                                              float ec, float* kv_out = nullptr) {
-  return fused_ge1_v<EX>(a, Bc, u, h, w2, *reinterpret_cast<const f32x4*>(a.gzb + (size_t)u * DAD_C), a.eflag[u], ec,
-                         kv_out);
-}
-template <bool EX>
-__device__ __forceinline__ float fused_ge1(const DadReduceArgs& a, int Bc, int u, int h, const float (&w2)[4],
-                                           float* kv_out = nullptr) {
-  return fused_ge1_ec<EX>(a, Bc, u, h, w2, a.ge_ecda[(size_t)u * DAD_H + h], kv_out);
-}
-
-}  // namespace
-
-// ------------------------------------------------------------------- FP32 (parity mode)
-// grid = 6 column blocks x splits; wave = 32 columns x 256 rows of dW1.
-// v_mfma_f32_32x32x2_f32: A[i=h][k] = G[row k][h], B[k][j=d] = x[row k][d] (k = 2 rows).
-//
-// An f32 MFMA holds the SIMD's vector issue for its whole 64 cycles (PMC: zero VALU/MFMA
-// co-execution cycles), so every VALU instruction of the loop adds its 4+ cycles to the
-// MFMA time: the loop is built to issue as few as possible per MFMA.
-//   * G (256 h x 32 rows of the slab, = ReLU' bit ? dL/de_u[h] / len_u : 0) is built ONCE per
-//     workgroup into LDS (thread = h, double-buffered, one barrier per slab) and read as MFMA
-//     A operands with ds_read_b128 (4 row pairs per read), instead of every wave rebuilding
-//     all of it per MFMA (select + scale: 2-3 VALU per MFMA, and the fused dL/de per h).
-//   * x (rows 2j + kh at column d) is loaded one slab ahead through a buffer descriptor of the
-//     slab's valid rows (rows past the utterance read 0; one add per load for the address).
-// The strong branch's augmentation is regenerated per element (counter RNG or explicit noise).
-constexpr int F32_GP = 36;   // G tile pitch per h: [kh][16 pairs] + 4 floats (conflict-free b128 reads)
-
-// the scale of G: dL/de / len from a dL/de buffer (modular encoder backward), or rebuilt from
-// the tail's dL/dz and the ECDA rows (fused step, fused_ge1)
-enum { F32_GE = 1, F32_FUSED = 2 };
-
-struct F32X {
-  float x[16], n[16];
-};
-
-// this lane's x (and explicit noise) of slab s: rows 2j + kh, column d
-template <bool EXPLICIT, bool STORE>
-__device__ __forceinline__ void f32_xload(const DadWgradArgs& a, int s, int d, int kh, F32X& r) {
-  const SlabIdx q = wg_slab(a, s);
-  const int nval = min(DAD_SLAB, q.T - q.c * DAD_SLAB);   // rows of the slab inside the utterance
-#ifndef F32_BUFLOAD
-#define F32_BUFLOAD 1
-#endif
-  if constexpr (!STORE && F32_BUFLOAD) {
-    const float* X = (q.br ? a.xn : a.xc) + (q.row0 + (size_t)q.c * DAD_SLAB) * DAD_D;
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X), 0, nval * DAD_D * 4, 0x00020000);
-    // The row offset goes in voffset, not soffset: the range check compares voffset (+ the
-    // instruction offset) with num_records, so rows past the utterance read 0 and nothing is
-    // read past the slab.  (The builtin returns the raw bits: __uint_as_float, not a value
-    // conversion.)
-    const int vo = (kh * DAD_D + d) * 4;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-      r.x[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, vo + j * 2 * DAD_D * 4, 0, 0));
-    if constexpr (EXPLICIT) {
-      const float* N = a.ns + (q.row0 + (size_t)q.c * DAD_SLAB) * DAD_D;
-      const auto rn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(N), 0, nval * DAD_D * 4, 0x00020000);
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        r.n[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rn, vo + j * 2 * DAD_D * 4, 0, 0));
-    }
-  } else {
-    const float* X = q.br ? a.xn : a.xc;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int t = min(q.c * DAD_SLAB + 2 * j + kh, q.T - 1);
-      r.x[j] = X[dad_src_row(a.src, q.br, q.b, q.T, t) * DAD_D + d];
-      if constexpr (EXPLICIT) r.n[j] = a.ns[(q.row0 + t) * DAD_D + d];
-    }
-  }
-}
-
-// G inputs of thread h for slab s: the ReLU' row mask and the ECDA row / dL/de value
-struct F32GIn {
-  uint32_t mw;
-  float ec;
-};
-template <int MODE>
-__device__ __forceinline__ void f32_gload(const DadWgradArgs& a, const DadReduceArgs& ra, int s, int h, F32GIn& r) {
-  const SlabIdx q = wg_slab(a, s);
-  r.mw = a.bits[q.bits_slab * DAD_H + h];
-  r.ec = 0.0f;
-  if constexpr (MODE == F32_GE) r.ec = a.ge[(size_t)q.erow * DAD_H + h];
-  if constexpr (MODE == F32_FUSED) r.ec = ra.ge_ecda[(size_t)q.erow * DAD_H + h];
-}
-
-// G^T of slab s into LDS: thread h writes G[h][kh][j] = bit (2j + kh) of its mask ? scale : 0
-template <int MODE, bool KEEPX>
-__device__ __forceinline__ void f32_gbuild(const DadWgradArgs& a, const DadReduceArgs& ra, int s, int h,
-                                           const float (&w2h)[4], const F32GIn& gi, float* G) {
-  const SlabIdx q = wg_slab(a, s);
-  float scale = 0.0f;
-  if constexpr (MODE == F32_GE) scale = gi.ec / fmaxf(a.vlen[q.erow], 1.0f);
-  if constexpr (MODE == F32_FUSED) {
-    // dL/de_u[h] / max(1, len_u), as dad_wgrad_direct builds it (16-bit there, f32 here)
-    const int u = q.erow;
-    const f32x4 gz = *reinterpret_cast<const f32x4*>(ra.gzb + (size_t)u * DAD_C);
-    scale = fused_ge1_v<KEEPX>(ra, a.g.Bc, u, h, w2h, gz, ra.eflag[u], gi.ec) / fmaxf(ra.vlen[u], 1.0f);
-  }
-  const uint32_t sb = __float_as_uint(scale);
-#pragma unroll
-  for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-      f32x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        v[e] = __uint_as_float((uint32_t)__builtin_amdgcn_sbfe((int)gi.mw, 2 * (4 * q4 + e) + kh, 1) & sb);
-      *reinterpret_cast<f32x4*>(G + h * F32_GP + kh * 16 + 4 * q4) = v;
-    }
-}
-
-// one slab's 128 MFMAs of this wave: A from the LDS G tile, B = x (strong: augmented here)
-template <bool EXPLICIT, bool STRONG>
-__device__ __forceinline__ void f32_mma(const DadWgradArgs& a, const SlabIdx& q, int d, int kh, float fkeep, int st,
-                                        const float* G, const F32X& r, f32x16 (&acc)[DAD_HT]) {
-  const int lane = threadIdx.x & 63;
-  const float* gl = G + (lane & 31) * F32_GP + kh * 16;
-#pragma unroll
-  for (int q4 = 0; q4 < 4; ++q4) {
-    f32x4 gv[DAD_HT];
-#pragma unroll
-    for (int ht = 0; ht < DAD_HT; ++ht) gv[ht] = *reinterpret_cast<const f32x4*>(gl + ht * 32 * F32_GP + 4 * q4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int j = 4 * q4 + e;
-      float x = r.x[j];
-      if constexpr (STRONG) {
-        const int t = q.c * DAD_SLAB + 2 * j + kh;
-        const bool tin = t < q.T;
-        const size_t grow = q.row0 + (tin ? t : 0);
-        const float n = EXPLICIT ? r.n[j] : dad_normal1(a.key_strong, (uint32_t)(grow * DAD_D + d));
-        const float sn = n * a.strong_std;
-        x = (x + sn) * fkeep;
-        x = (t >= st && t < st + a.mask_len) ? 0.0f : x;   // (st + mask_len <= st when mask_len = 0)
-        x = tin ? x : 0.0f;
-      }
-#pragma unroll
-      for (int ht = 0; ht < DAD_HT; ++ht) acc[ht] = __builtin_amdgcn_mfma_f32_32x32x2f32(gv[ht][e], x, acc[ht], 0, 0, 0);
-    }
-  }
-}
-
-template <bool EXPLICIT, int MODE, bool STORE, bool KEEPX>
-__device__ __forceinline__ void wgrad_f32_body(const DadWgradArgs& a, const DadReduceArgs& ra, float* Gs) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int i = lane & 31, kh = lane >> 5;
-  const int h = tid;   // (256 threads = the 256 hidden units, for the G tile)
-  float w2h[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if constexpr (MODE == F32_FUSED)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) w2h[c] = ra.student[DAD_OFF_W2 + c * DAD_H + h];
-  for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-    const int dblk = tile % 6, split = tile / 6;
-    const int d = (dblk * 4 + wv) * 32 + i;
-    int s0, s1;
-    wg_range(a, split, s0, s1);
-    f32x16 acc[DAD_HT];
-#pragma unroll
-    for (int ht = 0; ht < DAD_HT; ++ht) acc[ht] = f32x16{};
-    const float fkeep = wg_featkeep(a, d);   // (the strong branch's feature mask; clean rows ignore it)
-    if (s0 < s1) {
-      F32GIn gi, gn;
-      F32X cur, nxt;
-      f32_gload<MODE>(a, ra, s0, h, gi);
-      f32_xload<EXPLICIT, STORE>(a, s0, d, kh, cur);
-      f32_gload<MODE>(a, ra, min(s0 + 1, s1 - 1), h, gn);
-      f32_gbuild<MODE, KEEPX>(a, ra, s0, h, w2h, gi, Gs);
-      f32_xload<EXPLICIT, STORE>(a, min(s0 + 1, s1 - 1), d, kh, nxt);
-      __syncthreads();
-      for (int s = s0; s < s1; ++s) {
-        const int buf = (s - s0) & 1;
-        const SlabIdx q = wg_slab(a, s);
-        const float* G = Gs + buf * (DAD_H * F32_GP);
-        if (q.br) {
-          const int st = a.mask_len > 0 ? (EXPLICIT ? (int)a.start[q.b] : dad_tstart_at(a.key_tstart, q.b, a.start_hi)) : 0;
-          f32_mma<EXPLICIT, true>(a, q, d, kh, fkeep, st, G, cur, acc);
-        } else {
-          f32_mma<EXPLICIT, false>(a, q, d, kh, fkeep, 0, G, cur, acc);
-        }
-        // the next slab's G (its inputs loaded a slab ago), then the loads of slab s + 2
-        if (s + 1 < s1) f32_gbuild<MODE, KEEPX>(a, ra, s + 1, h, w2h, gn, Gs + (buf ^ 1) * (DAD_H * F32_GP));
-        cur = nxt;
-        f32_gload<MODE>(a, ra, min(s + 2, s1 - 1), h, gn);
-        f32_xload<EXPLICIT, STORE>(a, min(s + 2, s1 - 1), d, kh, nxt);
-        __syncthreads();
-      }
-    }
-    float* out = a.wpart + (size_t)split * DAD_H * DAD_D;
-#pragma unroll
-    for (int ht = 0; ht < DAD_HT; ++ht)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) out[(size_t)(ht * 32 + dad_acc_row(r, kh)) * DAD_D + d] = acc[ht][r];
-  }
-}
-
-// KEEPX: explicit classifier-dropout masks (fused mode only)
-template <bool EXPLICIT, int MODE, bool KEEPX>
-__device__ __forceinline__ void wgrad_f32_store(const DadWgradArgs& a, const DadReduceArgs& ra, float* Gs) {
-  if (a.src.rowc != nullptr) wgrad_f32_body<EXPLICIT, MODE, true, KEEPX>(a, ra, Gs);
-  else wgrad_f32_body<EXPLICIT, MODE, false, KEEPX>(a, ra, Gs);
-}
-template <bool EXPLICIT>
-__device__ __forceinline__ void wgrad_f32_mode(const DadWgradArgs& a, const DadReduceArgs& ra, float* Gs) {
-  if (ra.gzb == nullptr) wgrad_f32_store<EXPLICIT, F32_GE, false>(a, ra, Gs);
-  else if (ra.keep1) wgrad_f32_store<EXPLICIT, F32_FUSED, true>(a, ra, Gs);
-  else wgrad_f32_store<EXPLICIT, F32_FUSED, false>(a, ra, Gs);
-}
-
-#ifndef DAD_WGRAD_RG   // (wgrad_rg.hip holds the ragged siblings of the direct kernels only)
-__global__ __launch_bounds__(DAD_WGRAD_THREADS) void dad_wgrad_f32(DadWgradArgs a, DadReduceArgs ra) {
-  DAD_GUARD_BLOCK(DAD_WGRAD_THREADS);
-  static_assert(DAD_WGRAD_THREADS == DAD_H, "dad_wgrad_f32: thread = hidden unit for the G tile");
-  __shared__ __attribute__((aligned(16))) float Gs[2 * DAD_H * F32_GP];
-  if (a.ns) wgrad_f32_mode<true>(a, ra, Gs);
-  else wgrad_f32_mode<false>(a, ra, Gs);
-}
-#endif
 
 // ------------------------------------------------------- FP16 / BF16 (throughput modes)
 // Direct split-K GEMM after the losses: dW1 = sum_rows G[row]^T x[row] with
@@ -336,12 +40,14 @@ __global__ __launch_bounds__(DAD_WGRAD_THREADS) void dad_wgrad_f32(DadWgradArgs 
 static_assert(WGD_THREADS == 256 * WGD_GROUPS && DAD_H == 256, "dad_wgrad_direct: groups of 256 threads, thread = h");
 static_assert(WGD_GROUPS == 1 || WGD_GROUPS == 2, "dad_wgrad_direct: one or two slab groups");
 static_assert(WGD_DB == 64 && DAD_D % WGD_DB == 0, "dad_wgrad_direct: 8 threads x 8 columns per row");
-// per-workgroup cycles of wave 0 in the stamps build (dad_probe.h): [prologue, loop, epilogue,
-// -, sum over rounds of: compute+stage+load, barrier, -, -, rounds]
-DAD_PROBE_BUFFER(wgd_stamps, 512 * 10)
-#define WGD_CLK() DAD_PROBE_CLK()
-#define WGD_ACC(k, v) \
-  if (threadIdx.x == 0 && blockIdx.x < 512) DAD_PROBE_ADD(wgd_stamps, blockIdx.x * 10 + (k), (v))
+// what a launch converts of the NEXT step's clean rows besides its GEMM (wgd_tile, CP)
+enum WgdCp {
+  WGD_CP_NONE,      // nothing: the step does not name its next batch
+  WGD_CP_PADDED,    // a padded next batch
+  WGD_CP_STORE,     // a store batch (Bc <= 64): source rows through the utterance table held in registers
+  WGD_CP_STORE16,   // ... whose rows are read from an fp16 / bf16 store in place (the `_s16` kernels)
+};
+
 namespace {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -394,19 +100,16 @@ struct WgdTable {
 };
 
 __device__ __forceinline__ WgdTable wgd_table(const DadGeom& g, int s, int u0) {
-  const int nsc = g.Bc * g.ncc;
-  const bool br = s >= nsc;
-  const int rem = br ? s - nsc : s;
-  const int nc = br ? g.ncn : g.ncc;
-  const int b = rem / nc, c = rem - b * nc;
-  const int T = br ? g.Tn : g.Tc;
+  const SlabIdx q = wg_slab(g, s);
+  const bool br = q.br;
+  const int b = q.b, c = q.c, T = br ? g.Tn : g.Tc;
   WgdTable t;
   t.row0 = (br ? g.Bc * g.Tc + b * T : b * T) + c * DAD_SLAB;
   t.info = (((br ? g.Bc + b : b) - u0) << 8) | min(T - c * DAD_SLAB, DAD_SLAB);
   t.sd = s;
   return t;
 }
-// RG (the ragged step, wgrad_rg.hip): the lane's slab is live index k of the student list (live clean, then
+// RG (the ragged step, wgrad_direct_rg.hip): the lane's slab is live index k of the student list (live clean, then
 // live strong slabs; ps / pz: the live prefixes of dad_common.h over the n list utterances, in LDS).  The
 // utterance slot counts the utterances WITH a live slab from the split's first on (pz - zfirst), by order
 // of appearance: utterances of length 0 between two live ones take no slot of the LDS dL/de table.
@@ -597,20 +300,50 @@ __device__ __forceinline__ void wgd_cp_store(const DadPrepArgs& a, int u, uint32
 // x-tile LDS buffers per slab group: a slab is staged two rounds before it is read, one barrier
 // per two rounds (eight buffers and a barrier every four rounds measured neutral, round 3)
 constexpr int WGD_NBUF = 4;
+// LDS of the weight-gradient workgroups (160 KB with the dL/de table): the x tiles, then the
+// mask table; the end-of-tile exchange (red, 64 KB) reuses the x tiles and the spare space
+// after them (the table stays intact for the next tile)
+constexpr int WGD_XT = WGD_GROUPS * WGD_NBUF * DAD_SLAB * WGD_XP;   // 16-bit elements
+constexpr int WGD_RED = WGD_GROUPS == 2 ? DAD_H * WGD_DB : 1;
+struct __attribute__((aligned(16))) WgdSmem {
+  uint4 lut[WGD_LUT];   // first: its 64 KB sit at LDS offsets 0 .. 65535, so a table read needs no base add
+                        // (the ds_read offset field holds 16 bits)
+  union {
+    uint16_t xt[WGD_XT];
+    float red[WGD_RED];
+  } a;
+};
+
+// what the calls of wgd_tile share besides the launch's arguments and the workgroup's LDS (S, and the dL/de
+// table gs: LDS pointers held in a struct compile to generic accesses)
+struct WgdCtx {
+  int s0, s1, dbase;   // the tile: slabs [s0, s1), columns dbase .. dbase + WGD_DB - 1
+  float* outf;         // the split's partial
+  int gw, GW;          // CP: this wave's index among the GW waves that convert
+  const int* lps;      // RG: the live prefixes over the ln_ list utterances
+  const int* lpz;
+  int ln_;
+};
+
 // one 256 h x WGD_DB d tile over slabs [s0, s1): fp32 partial
 // CP: this launch also converts the NEXT step's clean rows into its prepared set (pc, when the
 // step names its next batch): wave gw of GW takes rows gw, gw + GW, ...; two rows' loads go out in
 // the first round of each block of NB rounds and are converted and stored at the start of the next
 // block (an HBM miss under this load takes about as long as NB rounds); the rows left after the
-// loop follow it.  CP = 1: padded next batch; CP = 2: store batch (Bc <= 64), source rows through
+// loop follow it.  CP (WgdCp): a padded next batch, or a store batch (Bc <= 64), source rows through
 // the utterance table held in registers (StoreRowsW), rows of type SC (a 16-bit store is read in place).
 // RG (the ragged step): [s0, s1) is a range of the live student list, lps / lpz its live prefixes over the
 // ln_ list utterances (in the x tiles' LDS, read in the prologue only, before the first slab is staged).
-template <bool F16, int CP, typename SC = float, bool RG = false>
-__device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceArgs& ra, int s0, int s1, int dbase,
-                                         float* outf, uint16_t* Xt, const uint4* lut, uint16_t* gs, float* red,
-                                         const DadPrepArgs& pc, int gw, int GW, const int* lps = nullptr,
-                                         const int* lpz = nullptr, int ln_ = 0) {
+template <bool F16, WgdCp CP, typename SC, bool RG>
+__device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceArgs& ra, const DadPrepArgs& pc,
+                                         const WgdCtx& t, WgdSmem& S, uint16_t* gs) {
+  uint16_t* const Xt = S.a.xt;
+  const uint4* const lut = S.lut;
+  float* const red = S.a.red;
+  const int s0 = t.s0, s1 = t.s1, dbase = t.dbase, gw = t.gw, GW = t.GW, ln_ = t.ln_;
+  float* const outf = t.outf;
+  const int* const lps = t.lps;
+  const int* const lpz = t.lpz;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
   const int grp = __builtin_amdgcn_readfirstlane(tid >> 8);
@@ -623,8 +356,7 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
   float unscale = 1.0f;   // FP16: 2^-s_h of row h = 64 wv + lane
   const uint32_t cploff = (uint32_t)lane * (4u * sizeof(SC)), cpsoff = (uint32_t)lane * 8u;   // CP: a row's lane columns
   typedef typename DadSrc<SC>::raw CpRaw;
-  for (int k = 0; DAD_PROBE_ON && k < 10; ++k)
-    if (tid == 0 && blockIdx.x < 512) DAD_PROBE_SET(wgd_stamps, blockIdx.x * 10 + k, 0);
+  WGD_ZERO();
   const unsigned long long t0 = WGD_CLK();
   unsigned long long t1 = t0, t2 = t0;
   if (s0 < s1) {
@@ -801,7 +533,7 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
     round(0, 0, false, mine > 0, SD < mine, false);
     int j = 1;
     int prow = gw;        // CP: this wave's next clean row of the next step
-    const StoreRowsW srw = CP == 2 ? dad_store_rows_w(pc, lane) : StoreRowsW{};
+    const StoreRowsW srw = CP == WGD_CP_STORE ? dad_store_rows_w(pc, lane) : StoreRowsW{};
     CpRaw pv[2][3];
     bool pending = false; // CP: rows prow - 2 GW, prow - GW loaded, not yet stored
     CpRaw po[2][3];       // CP two blocks ahead: rows prow - 4 GW, prow - 3 GW (loaded two blocks ago)
@@ -809,7 +541,7 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
     for (; j + NB - 1 + SD < cntmin; j += NB) {   // every round stages slab j + k + SD < cntmin
 #pragma unroll
       for (int k = 0; k < NB; ++k) {
-        if constexpr (CP) {
+        if constexpr (CP != WGD_CP_NONE) {
           if (k == 0) {
             // the rows loaded two blocks (2 NB rounds) ago, then this block's two
             if (pend2) {
@@ -821,8 +553,8 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
 #pragma unroll
               for (int e = 0; e < 3; ++e) po[q][e] = pv[q][e];
             pend2 = pending;
-            wgd_cp_load<CP == 2, SC, RG>(pc, prow, cploff, pv[0], srw);
-            wgd_cp_load<CP == 2, SC, RG>(pc, prow + GW, cploff, pv[1], srw);
+            wgd_cp_load<CP == WGD_CP_STORE, SC, RG>(pc, prow, cploff, pv[0], srw);
+            wgd_cp_load<CP == WGD_CP_STORE, SC, RG>(pc, prow + GW, cploff, pv[1], srw);
             prow += 2 * GW;
             pending = true;
           }
@@ -835,7 +567,7 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
       if (j + k < nround)
         round(j + k, (k + 1) % NB, j + k - 1 < mine, j + k < mine, j + k + SD < mine, (k + 1) % SD == SD - 1);
     if (nround - 1 < mine) wgd_mma<F16>(F, acc);
-    if constexpr (CP) {
+    if constexpr (CP != WGD_CP_NONE) {
       if (pend2) {
         wgd_cp_store<F16, SC, RG>(pc, prow - 4 * GW, cpsoff, po[0], srw);
         wgd_cp_store<F16, SC, RG>(pc, prow - 3 * GW, cpsoff, po[1], srw);
@@ -845,16 +577,16 @@ __device__ __forceinline__ void wgd_tile(const DadWgradArgs& a, const DadReduceA
         wgd_cp_store<F16, SC, RG>(pc, prow - GW, cpsoff, pv[1], srw);
       }
       for (; prow < pc.g.Bc * pc.g.Tc; prow += GW) {   // the rows the loop left
-        wgd_cp_load<CP == 2, SC, RG>(pc, prow, cploff, pv[0], srw);
+        wgd_cp_load<CP == WGD_CP_STORE, SC, RG>(pc, prow, cploff, pv[0], srw);
         wgd_cp_store<F16, SC, RG>(pc, prow, cpsoff, pv[0], srw);
       }
     }
     t2 = WGD_CLK();
-  } else if constexpr (CP != 0) {
-    const StoreRowsW srw = CP == 2 ? dad_store_rows_w(pc, lane) : StoreRowsW{};
+  } else if constexpr (CP != WGD_CP_NONE) {
+    const StoreRowsW srw = CP == WGD_CP_STORE ? dad_store_rows_w(pc, lane) : StoreRowsW{};
     for (int prow = gw; prow < pc.g.Bc * pc.g.Tc; prow += GW) {
       CpRaw pv[3];
-      wgd_cp_load<CP == 2, SC, RG>(pc, prow, cploff, pv, srw);
+      wgd_cp_load<CP == WGD_CP_STORE, SC, RG>(pc, prow, cploff, pv, srw);
       wgd_cp_store<F16, SC, RG>(pc, prow, cpsoff, pv, srw);
     }
   }
@@ -907,38 +639,14 @@ __device__ __forceinline__ void wgd_lut(uint4* lut) {
   }
 }
 
-// LDS of the weight-gradient workgroups (160 KB with the dL/de table): the x tiles, then the
-// mask table; the end-of-tile exchange (red, 64 KB) reuses the x tiles and the spare space
-// after them (the table stays intact for the next tile)
-constexpr int WGD_XT = WGD_GROUPS * WGD_NBUF * DAD_SLAB * WGD_XP;   // 16-bit elements
-constexpr int WGD_RED = WGD_GROUPS == 2 ? DAD_H * WGD_DB : 1;
-struct __attribute__((aligned(16))) WgdSmem {
-  uint4 lut[WGD_LUT];   // first: its 64 KB sit at LDS offsets 0 .. 65535, so a table read needs no base add
-                        // (the ds_read offset field holds 16 bits)
-  union {
-    uint16_t xt[WGD_XT];
-    float red[WGD_RED];
-  } a;
-};
-
-// (a definition per unit: device code is linked per unit)
-#ifdef DAD_WGRAD_RG
-#define WGD_XLINK static
-#else
-#define WGD_XLINK
-#endif
-WGD_XLINK __device__ double extra_block(const DadReduceArgs& a, int e, int tid, float (*xs)[16][6]);
-
-
-// RG (wgrad_rg.hip, the ragged step): a split's range is its share of the LIVE student list (wg_range's
+// RG (wgrad_direct_rg.hip, the ragged step): a split's range is its share of the LIVE student list (wg_range's
 // formula on the live count: the host chose `splits` from the dense count, so a share holds at most
 // WGD_MAXU slabs); the live prefixes are built from the batch's device lengths in the x tiles' LDS.  A
 // split whose share is empty writes a zero partial.
-template <bool F16, int CP, bool RG = false>
+template <bool F16, WgdCp CP, bool RG>
 __device__ __forceinline__ void wgrad_direct_body(const DadWgradArgs& a, const DadReduceArgs& ra, const DadPrepArgs& pc) {
   __shared__ WgdSmem S;
   __shared__ __attribute__((aligned(16))) uint16_t gs[WGD_MAXU * DAD_H];
-  uint16_t* Xt = S.a.xt;
   // XCD-aware tile order (grid is a multiple of 8; workgroups go round-robin over the 8
   // XCDs): each XCD takes a consecutive run of tiles, so the column blocks of one split,
   // which read the same ReLU' row masks, share an L2
@@ -957,6 +665,10 @@ __device__ __forceinline__ void wgrad_direct_body(const DadWgradArgs& a, const D
     float (*xs)[16][6] = reinterpret_cast<float (*)[16][6]>(S.a.red) + 16 * half;
     constexpr int per_wg = DAD_REDUCE_XBLK / WGD_XWG;
     constexpr int NB = DAD_REDUCE_BLOCKS - DAD_REDUCE_XBLK;
+    // (Both iterations unrolled, as the compiler chose by itself when all these kernels and dad_reduce shared
+    // a unit, except in dad_wgrad_direct_f16_cps_rg, where it kept the loop: said here, so that the choice no
+    // longer follows from which other callers of extra_block a unit holds.)
+#pragma unroll(RG && F16 && CP != WGD_CP_NONE ? 1 : 2)
     for (int r = 0; r < per_wg; r += 2) {
       const int e = xi * per_wg + r + half;
       const double v = dad_wave_sum_d(extra_block(ra, e, htid, xs));
@@ -979,289 +691,47 @@ __device__ __forceinline__ void wgrad_direct_body(const DadWgradArgs& a, const D
     dad_live_prefix_lds(a.src.lenc, a.g.Bc, a.g.ncc, a.g.Tc, a.src.lenn, rg_bn, a.g.ncn, a.g.Tn, lps, lpss, lpz);
     dad_wg_share(lps[rg_n], a.splits, split, s0, s1);
   } else {
-    const int total = wg_total(a);
-    const int per = (total + a.splits - 1) / a.splits;
-    s0 = split * per;
-    s1 = min(total, s0 + per);
+    wg_range(a, split, s0, s1);
   }
   wgd_lut(S.lut);   // (the tile's first barrier orders it before the first read)
   const int gw = __builtin_amdgcn_readfirstlane(tile * (WGD_THREADS / 64) + (int)(threadIdx.x >> 6));
   float* const outf = a.wpart + (size_t)split * DAD_H * DAD_D;
   const int GW = a.ntiles * (WGD_THREADS / 64);
-  // CP = 3: the `_s16` sibling of the store variant, clean rows read from an fp16 / bf16 store in their
-  // own type (block-uniform); a kernel of its own, so that the f32 kernels hold the f32 code alone
+  const WgdCtx t{s0, s1, dblk * WGD_DB, outf, gw, GW, lps, lpz, rg_n};
+  // The clean rows' source type, block-uniform.  STORE16, the `_s16` sibling of the store variant, reads an
+  // fp16 / bf16 store in its own type: a kernel of its own, so that the f32 kernels hold the f32 code alone.
+  // A ragged launch's next batch, ragged too, is a store batch of any of the three types.
+  constexpr WgdCp CPT = CP == WGD_CP_STORE16 ? WGD_CP_STORE : CP;
+  constexpr bool S16 = CP == WGD_CP_STORE16 || (RG && CP != WGD_CP_NONE), S32 = CP != WGD_CP_STORE16;
   if constexpr (RG) {
-    // (CP = 2 here: the next batch, ragged too, is a store batch; its rows' type is block-uniform)
-    if constexpr (CP != 0) {
+    if constexpr (CP != WGD_CP_NONE) {
       if (pc.xc_type() == DAD_STORE_F16)
-        wgd_tile<F16, CP, _Float16, true>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW, lps, lpz, rg_n);
+        wgd_tile<F16, CPT, _Float16, RG>(a, ra, pc, t, S, gs);
       else if (pc.xc_type() == DAD_STORE_BF16)
-        wgd_tile<F16, CP, __bf16, true>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW, lps, lpz, rg_n);
+        wgd_tile<F16, CPT, __bf16, RG>(a, ra, pc, t, S, gs);
       else
-        wgd_tile<F16, CP, float, true>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW, lps, lpz, rg_n);
+        wgd_tile<F16, CPT, float, RG>(a, ra, pc, t, S, gs);
     } else {
-      wgd_tile<F16, 0, float, true>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW, lps, lpz, rg_n);
+      wgd_tile<F16, CPT, float, RG>(a, ra, pc, t, S, gs);
     }
-  } else if constexpr (CP == 3) {
+  } else if constexpr (CP == WGD_CP_STORE16) {
     if (pc.xc_type() == DAD_STORE_F16)
-      wgd_tile<F16, 2, _Float16>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW);
+      wgd_tile<F16, CPT, _Float16, RG>(a, ra, pc, t, S, gs);
     else
-      wgd_tile<F16, 2, __bf16>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW);
+      wgd_tile<F16, CPT, __bf16, RG>(a, ra, pc, t, S, gs);
   } else {
-    wgd_tile<F16, CP>(a, ra, s0, s1, dblk * WGD_DB, outf, Xt, S.lut, gs, S.a.red, pc, gw, GW);
+    wgd_tile<F16, CPT, float, RG>(a, ra, pc, t, S, gs);
   }
 }
 
-#ifdef DAD_WGRAD_RG
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_rg(DadWgradArgs a, DadReduceArgs ra) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<false, 0, true>(a, ra, DadPrepArgs{});
-}
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_f16_rg(DadWgradArgs a, DadReduceArgs ra) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<true, 0, true>(a, ra, DadPrepArgs{});
-}
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_cps_rg(DadWgradArgs a, DadReduceArgs ra,
-                                                                         DadPrepArgs pc) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<false, 2, true>(a, ra, pc);
-}
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_f16_cps_rg(DadWgradArgs a, DadReduceArgs ra,
-                                                                             DadPrepArgs pc) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<true, 2, true>(a, ra, pc);
-}
-#else
-
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct(DadWgradArgs a, DadReduceArgs ra) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<false, 0>(a, ra, DadPrepArgs{});
-}
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_f16(DadWgradArgs a, DadReduceArgs ra) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<true, 0>(a, ra, DadPrepArgs{});
-}
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_cp(DadWgradArgs a, DadReduceArgs ra, DadPrepArgs pc) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<false, 1>(a, ra, pc);
-}
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_f16_cp(DadWgradArgs a, DadReduceArgs ra,
-                                                                         DadPrepArgs pc) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<true, 1>(a, ra, pc);
-}
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_cps(DadWgradArgs a, DadReduceArgs ra, DadPrepArgs pc) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<false, 2>(a, ra, pc);
-}
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_f16_cps(DadWgradArgs a, DadReduceArgs ra,
-                                                                          DadPrepArgs pc) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<true, 2>(a, ra, pc);
-}
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_cps_s16(DadWgradArgs a, DadReduceArgs ra,
-                                                                          DadPrepArgs pc) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<false, 3>(a, ra, pc);
-}
-__global__ __launch_bounds__(WGD_THREADS, 1) void dad_wgrad_direct_f16_cps_s16(DadWgradArgs a, DadReduceArgs ra,
-                                                                              DadPrepArgs pc) {
-  DAD_GUARD_BLOCK(WGD_THREADS);
-  wgrad_direct_body<true, 3>(a, ra, pc);
-}
-#endif   // DAD_WGRAD_RG
-
-// ---------------------------------------------------------------- reduce + squared norms
-// blocks [0, NB): DAD_REDUCE_COLS floats of dW1 each (+ squared-norm partial).
-// blocks NB + e, e < DAD_REDUCE_XBLK: hidden units 16e .. 16e+15 of
-//   db1[h]    = sum_r dL/de[r][h] / max(1, len_r) * active_count[r][h]      (autograd of b1)
-//   dW2[c][h] = sum_r dL/dz[r][c] * dropout(e_r)[h]   (fused step; the tail no longer does it)
-// their squared-norm share, and (e = 0) the b2 norm share and the loss totals
-// (I/train.py:462-466).  Thread = (hidden unit hl, row group rg): rows rg, rg+16, ...;
-// the 16 row groups are combined in fixed order (deterministic).
-static_assert(DAD_REDUCE_THREADS == 256 && DAD_H == 16 * DAD_REDUCE_XBLK, "extra blocks: 16 h x 16 row groups");
-
-// run by 256 threads (tid = 0..255 of a workgroup or of half of one), combining in xs
-template <bool EX>
-__device__ double extra_block_t(const DadReduceArgs& a, int e, int tid, float (*xs)[16][6]) {
-  const int hl = tid & 15, rg = tid >> 4;
-  const int h = 16 * e + hl;
-  const DadGeom& g = a.g;
-  const int nb = g.Bc + (a.warmup ? 0 : g.Bn);
-  const bool fused = a.gzb != nullptr;
-  const bool ecda = a.ge_ecda != nullptr;
-  float w2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (fused)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) w2[c] = a.student[DAD_OFF_W2 + c * DAD_H + h];
-  float db = 0.0f, gw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  // rows rg, rg + 16, ... in batches of 8 whose loads are all issued before any is used
-  // (index clamped, contribution masked): one memory round trip per batch, not per row
-  for (int r0 = rg; r0 < nb; r0 += 16 * 8) {
-    float gv[8], kv[8], rl[8], ct[8], em[8];
-    f32x4 gzv[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int r = min(r0 + 16 * k, nb - 1);
-      kv[k] = 1.0f;
-      if (fused) {
-        gv[k] = fused_ge1<EX>(a, g.Bc, r, h, w2, &kv[k]);
-        const int erow = r >= g.Bc ? g.Bn + r : r;   // strong row b lives at Bc + Bn + b
-        em[k] = a.emb[(size_t)erow * DAD_H + h];
-        gzv[k] = *reinterpret_cast<const f32x4*>(a.gzb + (size_t)r * DAD_C);
-      } else {
-        gv[k] = a.ge[(size_t)r * DAD_H + h];
-        if (ecda) gv[k] += a.ge_ecda[(size_t)r * DAD_H + h];
-        em[k] = 0.0f;
-        gzv[k] = f32x4{};
-      }
-      rl[k] = a.vlen[r];
-      ct[k] = a.cnt_tot[(size_t)r * DAD_H + h];
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (r0 + 16 * k >= nb) break;
-      db += gv[k] / fmaxf(rl[k], 1.0f) * ct[k];
-      if (fused) {
-        // dW2[c][h] = sum_u dL/dz[u][c] * dropout(e_u)[h]  (student clean / strong embeddings)
-        const float d = em[k] * kv[k];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) gw[c] += gzv[k][c] * d;
-      }
-    }
+// the entry points: one line each in the including unit (without / with a next batch to convert)
+#define WGD_KERNEL(name, F16, RG)                                                                   \
+  __global__ __launch_bounds__(WGD_THREADS, 1) void name(DadWgradArgs a, DadReduceArgs ra) {        \
+    DAD_GUARD_BLOCK(WGD_THREADS);                                                                   \
+    wgrad_direct_body<F16, WGD_CP_NONE, RG>(a, ra, DadPrepArgs{});                                  \
   }
-  xs[rg][hl][0] = db;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) xs[rg][hl][1 + c] = gw[c];
-  __syncthreads();
-  double sq = 0.0;
-  if (tid < 16 * 5) {
-    const int k = tid >> 4, hh = tid & 15;   // k: 0 = db1, 1..4 = dW2 row c = k-1
-    float v = xs[0][hh][k];
-    for (int q = 1; q < 16; ++q) v += xs[q][hh][k];
-    if (k == 0) {
-      a.grad[DAD_OFF_B1 + 16 * e + hh] = v;
-      sq = (double)v * v;
-    } else if (a.tailf) {
-      if (fused) a.grad[DAD_OFF_W2 + (k - 1) * DAD_H + 16 * e + hh] = v;
-      else v = a.grad[DAD_OFF_W2 + (k - 1) * DAD_H + 16 * e + hh];
-      sq = (double)v * v;
-    }
+#define WGD_KERNEL_CP(name, F16, CP, RG)                                                                     \
+  __global__ __launch_bounds__(WGD_THREADS, 1) void name(DadWgradArgs a, DadReduceArgs ra, DadPrepArgs pc) { \
+    DAD_GUARD_BLOCK(WGD_THREADS);                                                                            \
+    wgrad_direct_body<F16, CP, RG>(a, ra, pc);                                                               \
   }
-  if (e == 0 && a.tailf && tid >= 96 && tid < 100) {
-    const float gb = a.grad[DAD_OFF_B2 + tid - 96];
-    sq += (double)gb * gb;
-  }
-  if (e == 0 && a.tailf && tid == 128) {
-    const float* tf = a.tailf;
-    const float ecda_l = ((tf[DAD_T_ECDA_TERM] + tf[DAD_T_ECDA_TERM + 1]) + tf[DAD_T_ECDA_TERM + 2]) +
-                         tf[DAD_T_ECDA_TERM + 3];
-    const float ce = tf[DAD_T_CE], kl = tf[DAD_T_KL];
-    float* ex = a.grad + DAD_NPARAM;
-    // a pooling timeout in the tail launch (DAD_POOL_ABORT): NaN total, so dad_optim (on every DP
-    // rank, after the all-reduce) skips this step's update
-    const bool abort = a.pool_abort != nullptr && __hip_atomic_load(a.pool_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-    ex[12] = abort ? __builtin_nanf("") : ce + a.w_kl * kl + a.w_ecda * ecda_l;
-    ex[13] = ce;
-    ex[14] = kl;
-    ex[15] = ecda_l;
-  }
-  return sq;
-}
-WGD_XLINK __device__ double extra_block(const DadReduceArgs& a, int e, int tid, float (*xs)[16][6]) {
-  return a.keep1 ? extra_block_t<true>(a, e, tid, xs) : extra_block_t<false>(a, e, tid, xs);
-}
-
-#ifndef DAD_WGRAD_RG
-static_assert(DAD_REDUCE_THREADS == 4 * (DAD_REDUCE_COLS / 4), "dad_reduce: 4 split groups x float4 columns");
-static_assert(DAD_REDUCE_BLOCKS <= DAD_NORM_BLOCKS, "norm partials must fit the workspace");
-static_assert((DAD_NPARAM + 1023) / 1024 <= DAD_NORM_BLOCKS, "dad_norm partials must fit the workspace");
-__global__ __launch_bounds__(DAD_REDUCE_THREADS) void dad_reduce(DadReduceArgs a) {
-  DAD_GUARD_BLOCK(DAD_REDUCE_THREADS);
-  __shared__ double red[DAD_REDUCE_THREADS / 64];
-  __shared__ f32x4 part[4][DAD_REDUCE_COLS / 4 > DAD_H / 4 ? DAD_REDUCE_COLS / 4 : DAD_H / 4];
-  const int tid = threadIdx.x;
-  constexpr int NB = DAD_REDUCE_BLOCKS - DAD_REDUCE_XBLK;
-  double sq = 0.0;
-  if (blockIdx.x < NB) {
-    const int col = tid & (DAD_REDUCE_COLS / 4 - 1), kg = tid / (DAD_REDUCE_COLS / 4);
-    const size_t e0 = (size_t)blockIdx.x * DAD_REDUCE_COLS + (size_t)col * 4;
-    f32x4 s = f32x4{};
-#pragma unroll 4
-    for (int k = kg; k < a.splits; k += 4) s += *reinterpret_cast<const f32x4*>(a.wpart + (size_t)k * DAD_H * DAD_D + e0);
-    part[kg][col] = s;
-    __syncthreads();
-    if (kg == 0) {
-      const f32x4 t = ((part[0][col] + part[1][col]) + part[2][col]) + part[3][col];
-      *reinterpret_cast<f32x4*>(a.grad + DAD_OFF_W1 + e0) = t;
-      for (int e = 0; e < 4; ++e) sq += (double)t[e] * t[e];
-    }
-  } else {
-    __shared__ float xsx[16][16][6];
-    sq = extra_block(a, blockIdx.x - NB, tid, xsx);
-  }
-  if (!a.want_norm) return;
-  double v = dad_wave_sum_d(sq);
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    for (int k = 0; k < DAD_REDUCE_THREADS / 64; ++k) t += red[k];
-    a.normpart[blockIdx.x] = (float)t;
-  }
-}
-
-// FP16/BF16 step (the extra blocks ran on spare dad_wgrad_direct workgroups): one wave per
-// DAD_REDUCE_COLS columns, 4 per lane, the splits summed in split order with every partial's
-// load issued first (batches of 8, index clamped, +0 past the last split), the squared-norm
-// partial a wave reduction: no LDS, no barrier (dad_reduce's 4 row groups met through LDS
-// twice).
-static_assert(DAD_REDUCE_COLS == 4 * 64, "dad_reduce_w: one wave, 4 columns per lane");
-__global__ __launch_bounds__(64) void dad_reduce_w(DadReduceArgs a) {
-  DAD_GUARD_BLOCK(64);
-  const int lane = threadIdx.x;
-  const size_t e0 = (size_t)blockIdx.x * DAD_REDUCE_COLS + 4 * (size_t)lane;
-  constexpr int KB = 8;
-  f32x4 t = f32x4{};
-  for (int k0 = 0; k0 < a.splits; k0 += KB) {
-    f32x4 v[KB];
-#pragma unroll
-    for (int k = 0; k < KB; ++k)
-      v[k] = *reinterpret_cast<const f32x4*>(a.wpart + (size_t)min(k0 + k, a.splits - 1) * DAD_H * DAD_D + e0);
-#pragma unroll
-    for (int k = 0; k < KB; ++k) t += k0 + k < a.splits ? v[k] : f32x4{};
-  }
-  *reinterpret_cast<f32x4*>(a.grad + DAD_OFF_W1 + e0) = t;
-  if (!a.want_norm) return;
-  double sq = 0.0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) sq += (double)t[e] * t[e];
-  sq = dad_wave_sum_d(sq);
-  if (lane == 0) a.normpart[blockIdx.x] = (float)sq;
-}
-
-// Data-parallel path: after the SUM all-reduce, average (grads, thresholds, losses) and
-// recompute the squared-norm partials over the averaged gradient.
-__global__ __launch_bounds__(256) void dad_norm(float* grad, float* normpart, float inv) {
-  __shared__ double red[4];
-  const int tid = threadIdx.x;
-  double sq = 0.0;
-  const size_t n0 = (size_t)blockIdx.x * 1024;
-  for (int k = 0; k < 4; ++k) {
-    const size_t e = n0 + (size_t)k * 256 + tid;
-    if (e < DAD_NPARAM) {
-      const float g = grad[e] * inv;
-      grad[e] = g;
-      sq += (double)g * g;
-    }
-  }
-  if (blockIdx.x == 0 && tid < DAD_GRAD_EXTRA) {
-    float* ex = grad + DAD_NPARAM;
-    if (tid < 4 || tid >= 12) ex[tid] *= inv;   // thresholds and losses are means; sums stay sums
-  }
-  double v = dad_wave_sum_d(sq);
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  if (tid == 0) normpart[blockIdx.x] = (float)(((red[0] + red[1]) + red[2]) + red[3]);
-}
-#endif   // DAD_WGRAD_RG

@@ -1,5 +1,5 @@
 """16-bit throughput modes (FP16 and BF16 operands: the W-stationary encoder, csrc/encode_ws.hip,
-and the direct weight gradient, csrc/wgrad.hip) against FP32.
+and the direct weight gradient, csrc/wgrad_direct.h) against FP32.
 
 Two references:
   * the NumPy oracle with the reference's injected draws (rng='explicit'), on the edge
