@@ -550,6 +550,80 @@ int dad_cluster_plan(int64_t n, int cus, int* row_tiles, int* chunks, int* tiles
 int dad_cluster_metrics_chunked(const float* emb, const int64_t* labels, int64_t n, double* out, float* sil,
                                 int chunks, void* workspace, void* stream);
 
+/* --- exact t-SNE of a split's embeddings (csrc/tsne.hip) ----------------------------------
+ * run_tsne (I/iemocap_plot_tsne.py:310-323): scikit-learn 1.7.2's TSNE(n_components=2, method='exact') on
+ * emb [n][256] (dad_eval_split's emb / t_emb), in the three stages of sklearn/manifold/_t_sne.py.  Every call
+ * only enqueues on `stream`, uses no floating-point atomics and takes every sum in a fixed order, so two
+ * calls on the same inputs write bit-identical outputs.  One workspace of dad_tsne_workspace_bytes(n) serves
+ * all three; it needs no initialisation.  2 <= n <= DAD_TS_MAX_N.
+ *
+ * P is [n][DAD_TS_LD(n)] floats (n rounded up to the tile; a 1 GiB matrix at DAD_TS_MAX_N): dense, bit-symmetric
+ * (P_ij and P_ji are the same bits), P_ii = 0; the calls below never use a padding column's value.
+ *
+ * dad_tsne_affinities = _joint_probabilities.  D_ij = max(|a_i|^2 + |a_j|^2 - 2 a_i.a_j, 0) on the fp32 matrix
+ * cores, a = the rows minus their fp32 mean, |a_i|^2 the diagonal of the same Gram block (D_ii and the distance of
+ * duplicate rows are exactly 0) -- the distances of dad_cluster_metrics, squared.  Per row, _binary_search_perplexity
+ * in double on the fp32 distances: beta from 1, doubled / halved until bracketed, then bisected, at most 100 steps,
+ * until |H - log(perplexity)| <= 1e-5, H = log(sum_j e^(-beta D_ij)) + beta sum_j D_ij c_ij over j != i, a sum of 0
+ * replaced by 1e-8; c_ij = e^(-beta D_ij) / sum.  Then P_ij = max((c_ij + c_ji) / max(sum, eps), eps), sum over all
+ * i != j in double, eps = 2.220446049250313e-16.  beta [n] doubles (device, may be NULL) receives each row's beta.
+ * A row of emb with a non-finite component is counted into the int32 at word DAD_TS_WS_NONFINITE of the workspace
+ * (P is then meaningless).  DAD_E_SHAPE: n < 2 or n > DAD_TS_MAX_N; DAD_E_ARG: emb, P or workspace is NULL, or
+ * perplexity not in (0, n) (scikit-learn's rule). */
+#define DAD_TS_MAX_N 16384      /* largest n */
+#define DAD_TS_TILE 64          /* rows / columns of a tile; P's row stride is a multiple of it */
+#define DAD_TS_LD(n) (((n) + DAD_TS_TILE - 1) / DAD_TS_TILE * DAD_TS_TILE)
+#define DAD_TS_MAX_CHUNKS 32    /* most column chunks a row tile is split into */
+#define DAD_TS_WS_NONFINITE 0   /* int32 word of the workspace: rows with a non-finite component (dad_tsne_affinities) */
+/* workspace bytes of the three calls (0 for an unsupported n) */
+size_t dad_tsne_workspace_bytes(int64_t n);
+int dad_tsne_affinities(const float* emb, int64_t n, double perplexity, float* P, double* beta, void* workspace,
+                        void* stream);
+/* dad_tsne_gradient = _kl_divergence with one degree of freedom, at Y [n][2] with p = exaggeration * P:
+ *   w_ij = 1 / (1 + |y_i - y_j|^2)  (from the differences, so coincident points give exactly 1),  Z = sum_{i != j} w_ij,
+ *   KL = sum_{i != j} p_ij (log p_ij - log w_ij) + log Z sum p_ij,
+ *   grad_i = 4 (sum_j p_ij w_ij (y_i - y_j) - sum_j w_ij^2 (y_i - y_j) / Z)        -> grad [n][2] floats.
+ * scikit-learn also clamps Q = max(w / Z, eps); the device does not (the clamp acts only where w n^2 < 2.2e-16 Z,
+ * an embedding some 1e7 times wider than its typical neighbour distance).  The per-row force sums are fp32; Z, KL and
+ * the gradient norm are reduced in double.  out: DAD_TS_SLOTS doubles (device). */
+#define DAD_TS_Z 0
+#define DAD_TS_KL 1             /* the error; after dad_tsne_run scikit-learn's kl_divergence_ */
+#define DAD_TS_GRAD_NORM 2      /* |grad| (dad_tsne_run: of the last iteration's gradient times its gains) */
+#define DAD_TS_N_ITER 3         /* dad_tsne_run: scikit-learn's n_iter_ (-1 until the run ends) */
+#define DAD_TS_N_CHECKS 4       /* dad_tsne_run: records written to history */
+#define DAD_TS_SLOTS 8
+/* DAD_E_ARG: a NULL pointer or exaggeration <= 0; DAD_E_SHAPE: n. */
+int dad_tsne_gradient(const float* P, int64_t n, const float* Y, double exaggeration, double* out, float* grad,
+                      void* workspace, void* stream);
+/* The grid of the n x n pass for n rows on a device of `cus` compute units: ceil(n / 64) row tiles, each split
+ * into `chunks` runs of tiles_per_chunk column tiles (the last may be shorter, none is empty), chunks <= min(row
+ * tiles, DAD_TS_MAX_CHUNKS).  Host only. */
+int dad_tsne_plan(int64_t n, int cus, int* row_tiles, int* chunks, int* tiles_per_chunk);
+/* dad_tsne_gradient with the chunk count asked for (clamped as dad_tsne_plan clamps it; <= 0: the plan's),
+ * for tests of the chunked summation at small n. */
+int dad_tsne_gradient_chunked(const float* P, int64_t n, const float* Y, double exaggeration, double* out,
+                              float* grad, int chunks, void* workspace, void* stream);
+/* dad_tsne_run = TSNE._tsne / _gradient_descent from Y (the initial embedding on entry, the result on exit):
+ * min(250, max_iter) exploration iterations at momentum 0.5 on early_exaggeration * P, then momentum 0.8 on P up to
+ * max_iter; per element gains += 0.2 where update * grad < 0, otherwise gains *= 0.8, floor 0.01; grad *= gains;
+ * update = momentum * update - learning_rate * grad; Y += update (fp32; gains start at 1 and the update at 0 in each
+ * phase).  At iterations with (i + 1) % 50 == 0 the error and |grad| go to history and the phase stops when
+ * i - best_iter > n_iter_without_progress (250 during exploration) without a new best error, or |grad| <=
+ * min_grad_norm; a stop during exploration moves on to the second phase at i + 1, a stop in the second phase ends the
+ * run.  The call enqueues max_iter iterations (one force and one step launch each); the iteration state lives in the
+ * workspace, and after the run has ended every remaining launch returns at its entry.  history receives
+ * [max_iter / 50 + 1][2] doubles (error, |grad|), DAD_TS_N_CHECKS of them written; out as above.
+ * DAD_E_ARG: a NULL pointer, max_iter < 1, n_iter_without_progress < 0, early_exaggeration or learning_rate <= 0. */
+typedef struct dad_tsne_args {
+  int32_t max_iter;                  /* scikit-learn: 1000 */
+  int32_t n_iter_without_progress;   /* 300 */
+  double early_exaggeration;         /* 12 */
+  double learning_rate;              /* 'auto' = max(n / early_exaggeration / 4, 50) */
+  double min_grad_norm;              /* 1e-7 */
+} dad_tsne_args;
+int dad_tsne_run(const float* P, int64_t n, float* Y, const dad_tsne_args* args, double* history, double* out,
+                 void* workspace, void* stream);
+
 /* --- the reference's helper types as operators (I/utils.py:317-652) -------------------
  * For trainer code that drives DataAugmentation / DACPManager / ECDALoss itself (the
  * train_step shim's callers, anchor calibration, I/train.py:334,341).  Same device functions

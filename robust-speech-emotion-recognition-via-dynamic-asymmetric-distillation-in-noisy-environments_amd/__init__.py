@@ -19,10 +19,12 @@ from .utils import DACPManager, DataAugmentation, ECDALoss
 from .trace import TrainingTrace
 from . import checkpoint, evaluate, pretrain
 from .evaluate import cluster_metrics, cluster_metrics_store, separation_report
+from .evaluate import tsne, tsne_affinities, tsne_gradient, tsne_report, tsne_store
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
            "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "TrainingTrace",
-           "cluster_metrics", "cluster_metrics_store", "separation_report", "build", "lib"]
+           "cluster_metrics", "cluster_metrics_store", "separation_report",
+           "tsne", "tsne_affinities", "tsne_gradient", "tsne_store", "tsne_report", "build", "lib"]
 
 
 def build(verbose=True):

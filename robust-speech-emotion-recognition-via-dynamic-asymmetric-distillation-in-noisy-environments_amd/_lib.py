@@ -36,6 +36,15 @@ TRACE_HDR_WORDS, TRACE_REC_WORDS, TRACE_MASKED_IN = 4, 4, 0x100   # dad.h DAD_TR
 CM_SILHOUETTE, CM_CH, CM_VALID, CM_M, CM_K, CM_COUNTS, CM_SIL_CLASS, CM_W, CM_B, CM_NONFINITE = 0, 1, 2, 3, 4, 5, 9, 13, 14, 15
 CM_SLOTS, CM_MAX_N, CM_TILE, CM_MAX_CHUNKS = 16, 65536, 64, 16
 
+# dad_tsne_* (dad.h DAD_TS_*): float64 slots of the out block, limits, the workspace word of the non-finite count
+TS_Z, TS_KL, TS_GRAD_NORM, TS_N_ITER, TS_N_CHECKS, TS_SLOTS = 0, 1, 2, 3, 4, 8
+TS_MAX_N, TS_TILE, TS_MAX_CHUNKS, TS_WS_NONFINITE = 16384, 64, 32, 0
+
+
+def ts_ld(n):
+    """dad.h DAD_TS_LD: the row stride of P."""
+    return (n + TS_TILE - 1) // TS_TILE * TS_TILE
+
 
 def tail_floats(bn):
     return DAD_TAIL_HDR + bn * 7
@@ -106,6 +115,12 @@ class DadEvalArgs(ctypes.Structure):
                   "score", "pred", "t_emb", "t_logits", "t_pred", "counts", "moments")]
                 + [("n", ctypes.c_int64), ("slabs", ctypes.c_int64), ("store_dtype", ctypes.c_int32),
                    ("use_entropy", ctypes.c_int32), ("precision", ctypes.c_int32), ("reserved", ctypes.c_int32)])
+
+
+class DadTsneArgs(ctypes.Structure):
+    _fields_ = [("max_iter", ctypes.c_int32), ("n_iter_without_progress", ctypes.c_int32),
+                ("early_exaggeration", ctypes.c_double), ("learning_rate", ctypes.c_double),
+                ("min_grad_norm", ctypes.c_double)]
 
 
 # exported symbols (must match include/dad.h); tests check every one is present
@@ -199,6 +214,18 @@ EXPORTS = {
                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "dad_cluster_metrics_chunked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_tsne_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "dad_tsne_affinities": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_tsne_gradient": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_tsne_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "dad_tsne_gradient_chunked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
+    "dad_tsne_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(DadTsneArgs),
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "dad_timing_start": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "dad_timing_kernels": (ctypes.c_int, [ctypes.c_uint]),
     "dad_timing_reset": (ctypes.c_int, []),
@@ -216,7 +243,8 @@ EXPORTS = {
 # the feature that needs one reports the stale build when it is asked for (require()).
 OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_step_plan_kernels", "dad_trace_bytes", "dad_trace_append",
                     "dad_cluster_workspace_bytes", "dad_cluster_metrics", "dad_cluster_plan",
-                    "dad_cluster_metrics_chunked")
+                    "dad_cluster_metrics_chunked", "dad_tsne_workspace_bytes", "dad_tsne_affinities",
+                    "dad_tsne_gradient", "dad_tsne_plan", "dad_tsne_gradient_chunked", "dad_tsne_run")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

@@ -33,6 +33,7 @@
 // row); the other launches read the embeddings three more times.  DESIGN.md 6b has the measured figures.
 #include <cstdint>
 
+#include "cluster_gram.h"   // the Gram block: operand layout, staging and MFMA chain (shared with tsne.hip)
 #include "dad_common.h"
 
 int device_cus(int* out);   // dad_abi.hip
@@ -40,8 +41,8 @@ int device_cus(int* out);   // dad_abi.hip
 namespace {
 
 constexpr int kTile = DAD_CM_TILE;         // rows and columns of a tile
-constexpr int kLd = DAD_H + 4;             // LDS row stride of the column tile, floats
-constexpr int kThreads = 256;
+constexpr int kLd = kGramLd;               // LDS row stride of the column tile, floats
+constexpr int kThreads = kGramThreads;
 constexpr int kMaxChunks = DAD_CM_MAX_CHUNKS;
 
 static_assert(kTile == 64 && DAD_H == 256 && DAD_C == 4, "the pair kernel's wave / lane mapping");
@@ -207,15 +208,7 @@ __global__ __launch_bounds__(kThreads, 2) void dad_cluster_pair(ClusterPairArgs 
 
   // A operand: row i0 + 32 rh + l32; MFMA step e of k-block q takes k = 8 q + 4 kh + e on both operands
   f32x4 av[DAD_H / 8];
-  {
-    const int ia = i0 + 32 * rh + l32;
-    const float* ra = a.emb + (size_t)(ia < n ? ia : 0) * DAD_H + 4 * kh;
-#pragma unroll
-    for (int q = 0; q < DAD_H / 8; ++q)
-      av[q] = ia < n ? *reinterpret_cast<const f32x4*>(ra + 8 * q) -
-                           *reinterpret_cast<const f32x4*>(a.mean + 4 * kh + 8 * q)
-                     : f32x4{};
-  }
+  dad_gram_load_a(av, a.emb, a.mean, i0 + 32 * rh + l32, n, kh);
   const f32x4 mu4 = *reinterpret_cast<const f32x4*>(a.mean + 4 * (tid & 63));   // the columns this thread stages
   if (tid < kTile) ni_s[tid] = a.norms[i0 + tid];
   float bins[16][DAD_C];
@@ -228,12 +221,7 @@ __global__ __launch_bounds__(kThreads, 2) void dad_cluster_pair(ClusterPairArgs 
   for (int t = chunk * a.per; t < t_end; ++t) {
     const int j0 = kTile * t;
     __syncthreads();      // the previous tile's operand reads are done
-#pragma unroll
-    for (int e = 0; e < kTile * (DAD_H / 4) / kThreads; ++e) {
-      const int idx = tid + kThreads * e, r = idx >> 6, c4 = 4 * (idx & 63), j = j0 + r;   // (idx & 63 = tid & 63)
-      const f32x4 v = j < n ? *reinterpret_cast<const f32x4*>(a.emb + (size_t)j * DAD_H + c4) - mu4 : f32x4{};
-      *reinterpret_cast<f32x4*>(&bt[r * kLd + c4]) = v;
-    }
+    dad_gram_stage(bt, a.emb, mu4, j0, n, tid);
     if (tid < kTile) {
       const int j = j0 + tid;
       nj_s[tid] = j < n ? a.norms[j] : 0.0f;
@@ -241,14 +229,7 @@ __global__ __launch_bounds__(kThreads, 2) void dad_cluster_pair(ClusterPairArgs 
     }
     __syncthreads();
     const int jc = 32 * ch + l32;
-    const float* rb = &bt[jc * kLd + 4 * kh];
-    f32x16 acc = f32x16{};
-#pragma unroll
-    for (int q = 0; q < DAD_H / 8; ++q) {
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(rb + 8 * q);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q][e], bv[e], acc, 0, 0, 0);
-    }
+    const f32x16 acc = dad_gram_block(av, bt, jc, kh);
     const int cj = lj_s[jc], jg = j0 + jc;
     const float nj = nj_s[jc];
 #pragma unroll

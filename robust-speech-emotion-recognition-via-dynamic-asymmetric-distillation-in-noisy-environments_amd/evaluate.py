@@ -20,6 +20,11 @@ and the class separation of a split's embeddings (dad_cluster_metrics, csrc/clus
   cluster_metrics, cluster_metrics_store, separation_report
                       calculate_cluster_metrics / generate_analysis_report's `cluster_analysis`
                       (I/iemocap_plot_tsne.py:390-398, 428-442)
+
+and the 2-D picture those scores describe (dad_tsne_*, csrc/tsne.hip):
+
+  tsne_affinities, tsne_gradient, tsne, tsne_store, tsne_report
+                      run_tsne: scikit-learn's TSNE(method='exact') (I/iemocap_plot_tsne.py:310-323, 524-525)
 """
 import warnings
 
@@ -512,3 +517,174 @@ def separation_report(initial_model, trained_model, store_or_loader):
     weights (student embeddings, as iemocap_plot_tsne.py embeds with)."""
     return separation_from_metrics(cluster_metrics_store(initial_model, store_or_loader),
                                    cluster_metrics_store(trained_model, store_or_loader))
+
+
+# ------------------------------------------------------------------ exact t-SNE of a split
+# run_tsne (I/iemocap_plot_tsne.py:310-323) copies the embeddings to the host and runs scikit-learn's TSNE,
+# once per weight set.  dad_tsne_* (csrc/tsne.hip) is scikit-learn's method='exact' in its three stages on the
+# device: the joint distribution P, one evaluation of the error and its gradient, and the 1,000-iteration
+# descent, which the host only enqueues.
+
+def _tsne_workspace(n, device):
+    fn = _lib.require("dad_tsne_workspace_bytes", "tsne")
+    need = int(fn(int(n)))
+    if need == 0:
+        raise ValueError("t-SNE takes 2 <= n <= %d rows, got %d" % (_lib.TS_MAX_N, n))
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _check_emb(emb):
+    if not torch.is_tensor(emb) or not emb.is_cuda or emb.dtype != torch.float32 or emb.dim() != 2 \
+            or emb.shape[1] != 256:
+        raise ValueError("emb must be a float32 device tensor [n, 256]")
+    return emb.contiguous()
+
+
+def _check_p(P):
+    if not torch.is_tensor(P) or not P.is_cuda or P.dtype != torch.float32 or P.dim() != 2 \
+            or P.shape[1] != _lib.ts_ld(P.shape[0]) or not P.is_contiguous():
+        raise ValueError("P must be a contiguous float32 device tensor [n, n rounded up to %d] (tsne_affinities)"
+                         % _lib.TS_TILE)
+    return P
+
+
+def _enqueue_tsne_affinities(emb, perplexity, P, beta, ws):
+    fn = _lib.require("dad_tsne_affinities", "tsne")
+    _lib.check(fn(_lib.ptr(emb), emb.shape[0], float(perplexity), _lib.ptr(P), _lib.ptr(beta), _lib.ptr(ws),
+                  torch.cuda.current_stream(emb.device).cuda_stream), "dad_tsne_affinities")
+
+
+def tsne_affinities(emb, perplexity=30.0, beta=False, _ws=None):
+    """scikit-learn's _joint_probabilities of emb [n, 256] (float32, device) on the device: the dense symmetric
+    joint distribution P as a float32 device tensor [n, n rounded up to 64] (P[:, :n] is the matrix; the padding
+    columns are 0).  beta=True returns (P, the float64 precision the search found for each row).  Raises
+    ValueError for n < 2, n > 16384 or a perplexity outside (0, n), before any launch, and DadError when a row
+    has a non-finite component."""
+    emb = _check_emb(emb)
+    n = emb.shape[0]
+    ws = _tsne_workspace(n, emb.device) if _ws is None else _ws
+    if not 0.0 < float(perplexity) < n:
+        raise ValueError("perplexity must be in (0, n = %d), got %r" % (n, perplexity))
+    P = torch.empty(n, _lib.ts_ld(n), dtype=torch.float32, device=emb.device)
+    b = torch.empty(n, dtype=torch.float64, device=emb.device) if beta else None
+    _enqueue_tsne_affinities(emb, perplexity, P, b, ws)
+    nbad = int(ws[4 * _lib.TS_WS_NONFINITE:4 * _lib.TS_WS_NONFINITE + 4].view(torch.int32).item())
+    if nbad > 0:
+        raise _lib.DadError("dad_tsne_affinities: %d of %d row(s) have a non-finite embedding component" % (nbad, n))
+    return (P, b) if beta else P
+
+
+def tsne_gradient(P, Y, exaggeration=1.0, _chunks=0, _ws=None):
+    """scikit-learn's _kl_divergence (one degree of freedom) at Y [n, 2] (float32, device) against
+    exaggeration * P (tsne_affinities' tensor): {'kl_divergence', 'z', 'grad_norm', 'grad' [n, 2] device
+    tensor}.  _chunks > 0 asks for that many column chunks per row tile instead of the planner's."""
+    P = _check_p(P)
+    n = P.shape[0]
+    if not torch.is_tensor(Y) or Y.device != P.device or Y.dtype != torch.float32 or tuple(Y.shape) != (n, 2):
+        raise ValueError("Y must be a float32 tensor [n, 2] on P's device")
+    Y = Y.contiguous()
+    ws = _tsne_workspace(n, P.device) if _ws is None else _ws
+    out = torch.empty(_lib.TS_SLOTS, dtype=torch.float64, device=P.device)
+    grad = torch.empty(n, 2, dtype=torch.float32, device=P.device)
+    fn = _lib.require("dad_tsne_gradient_chunked", "tsne")
+    _lib.check(fn(_lib.ptr(P), n, _lib.ptr(Y), float(exaggeration), _lib.ptr(out), _lib.ptr(grad), int(_chunks),
+                  _lib.ptr(ws), torch.cuda.current_stream(P.device).cuda_stream), "dad_tsne_gradient")
+    o = out.cpu().numpy()
+    return {"kl_divergence": float(o[_lib.TS_KL]), "z": float(o[_lib.TS_Z]), "grad_norm": float(o[_lib.TS_GRAD_NORM]),
+            "grad": grad}
+
+
+def tsne_pca_init(emb):
+    """TSNE's init='pca' with the exact components: the top two principal components of the centred rows, from an
+    eigendecomposition of the 256 x 256 covariance in float64 (scikit-learn draws them from its randomized solver,
+    which agrees to 3e-10 at a scale of 1.8e-4), each signed so that its largest-magnitude loading is positive
+    (svd_flip(u_based_decision=False)), cast to float32 and scaled so that column 0 has standard deviation 1e-4."""
+    x = emb.to(torch.float64)
+    xc = x - x.mean(0, keepdim=True)
+    _, v = torch.linalg.eigh(xc.T @ xc)
+    v = v[:, [-1, -2]]
+    big = v.gather(0, v.abs().argmax(0, keepdim=True))
+    v = v * torch.sign(big)
+    y = (xc @ v).to(torch.float32)
+    return (y / y[:, 0].std(unbiased=False) * 1e-4).contiguous()
+
+
+def tsne_run_buffers(n, max_iter, device):
+    """(history [max_iter // 50 + 1, 2], out [8]) float64 device tensors of dad_tsne_run."""
+    return (torch.zeros(int(max_iter) // 50 + 1, 2, dtype=torch.float64, device=device),
+            torch.zeros(_lib.TS_SLOTS, dtype=torch.float64, device=device))
+
+
+def enqueue_tsne_run(P, Y, history, out, ws, max_iter=1000, learning_rate="auto", early_exaggeration=12.0,
+                     min_grad_norm=1e-7, n_iter_without_progress=300):
+    """dad_tsne_run on the current stream, enqueue only (no copy, no synchronisation; graph-capturable): Y [n, 2]
+    holds the initial embedding and receives the result."""
+    n = P.shape[0]
+    a = _lib.DadTsneArgs()
+    a.max_iter, a.n_iter_without_progress = int(max_iter), int(n_iter_without_progress)
+    a.early_exaggeration = float(early_exaggeration)
+    a.learning_rate = (max(n / float(early_exaggeration) / 4.0, 50.0) if isinstance(learning_rate, str)
+                       else float(learning_rate))
+    a.min_grad_norm = float(min_grad_norm)
+    fn = _lib.require("dad_tsne_run", "tsne")
+    _lib.check(fn(_lib.ptr(P), n, _lib.ptr(Y), a, _lib.ptr(history), _lib.ptr(out), _lib.ptr(ws),
+                  torch.cuda.current_stream(P.device).cuda_stream), "dad_tsne_run")
+
+
+def tsne(emb, perplexity=30.0, max_iter=1000, init="pca", learning_rate="auto", early_exaggeration=12.0,
+         min_grad_norm=1e-7, n_iter_without_progress=300, history=False, _P=None):
+    """scikit-learn's TSNE(n_components=2, method='exact') of emb [n, 256] (float32, device) on the device, with
+    scikit-learn's parameters and defaults.  init: 'pca' (tsne_pca_init) or an [n, 2] tensor, used as given and
+    never modified ('random' is not offered).  learning_rate 'auto' = max(n / early_exaggeration / 4, 50).
+    Returns {'embedding' [n, 2] float32 device tensor, 'kl_divergence', 'n_iter'}; history=True adds 'history', the
+    (error, gradient norm) of every 50th iteration's check as a float64 array.  max_iter below 250 shortens the
+    exploration phase to max_iter iterations (scikit-learn refuses such a value)."""
+    emb = _check_emb(emb)
+    n = emb.shape[0]
+    if isinstance(init, str):
+        if init != "pca":
+            raise ValueError("init must be 'pca' or an [n, 2] tensor, got %r" % (init,))
+    elif not torch.is_tensor(init) or tuple(init.shape) != (n, 2):
+        raise ValueError("init must be 'pca' or an [n, 2] tensor")
+    if isinstance(learning_rate, str) and learning_rate != "auto":
+        raise ValueError("learning_rate must be 'auto' or a number")
+    if int(max_iter) < 1:
+        raise ValueError("max_iter must be at least 1")
+    ws = _tsne_workspace(n, emb.device)
+    P = tsne_affinities(emb, perplexity, _ws=ws) if _P is None else _check_p(_P)
+    Y = (tsne_pca_init(emb) if isinstance(init, str)
+         else init.detach().to(device=emb.device, dtype=torch.float32, copy=True).contiguous())
+    hist, out = tsne_run_buffers(n, max_iter, emb.device)
+    enqueue_tsne_run(P, Y, hist, out, ws, max_iter, learning_rate, early_exaggeration, min_grad_norm,
+                     n_iter_without_progress)
+    o = out.cpu().numpy()
+    res = {"embedding": Y, "kl_divergence": float(o[_lib.TS_KL]), "n_iter": int(o[_lib.TS_N_ITER])}
+    if history:
+        res["history"] = hist[:int(o[_lib.TS_N_CHECKS])].cpu().numpy()
+    return res
+
+
+def tsne_store(model, store_or_loader, use_teacher=False, precision="fp32", **tsne_args):
+    """tsne of the split's eval-mode embeddings (the teacher's with use_teacher), which dad_eval_split leaves on the
+    device: the embeddings never reach the host."""
+    model.eval()
+    plan = EvalPlan.of(store_or_loader)
+    name = "t_emb" if use_teacher else "emb"
+    emb = enqueue_eval_split(model, plan, use_teacher=use_teacher, precision=precision, outputs=(name,))[name]
+    return tsne(emb, **tsne_args)
+
+
+def tsne_report(initial_model, trained_model, store_or_loader, **tsne_args):
+    """The inputs of the reference's plot_tsne_comparison (I/iemocap_plot_tsne.py:524-525 and the plot call) for
+    one split: {'initial' [n, 2], 'trained' [n, 2] NumPy float32 embeddings under the two weight sets (student
+    embeddings, as iemocap_plot_tsne.py embeds with), 'labels' [n], 'class_counts' [4], 'kl_divergence' (initial,
+    trained), 'n_iter' (initial, trained)}."""
+    plan = EvalPlan.of(store_or_loader)
+    if plan.labels_d is None:
+        raise ValueError("the split has no labels")
+    a = tsne_store(initial_model, plan, **tsne_args)
+    b = tsne_store(trained_model, plan, **tsne_args)
+    labels = plan.labels_d.cpu().numpy()
+    return {"initial": a["embedding"].cpu().numpy(), "trained": b["embedding"].cpu().numpy(), "labels": labels,
+            "class_counts": [int((labels == c).sum()) for c in range(4)],
+            "kl_divergence": (a["kl_divergence"], b["kl_divergence"]), "n_iter": (a["n_iter"], b["n_iter"])}
