@@ -33,10 +33,8 @@
 // row); the other launches read the embeddings three more times.  DESIGN.md 6b has the measured figures.
 #include <cstdint>
 
-#include "cluster_gram.h"   // the Gram block: operand layout, staging and MFMA chain (shared with tsne.hip)
 #include "dad_common.h"
-
-int device_cus(int* out);   // dad_abi.hip
+#include "pairwise.h"   // the Gram block, the tile walk, the squared distance and the chunk plan (shared with tsne.hip)
 
 namespace {
 
@@ -75,7 +73,6 @@ ClusterWs cluster_ws_layout(int64_t n) {
 constexpr int kHN0 = 0, kHM = 4, kHK = 5, kHValid = 6, kHBad = 7;
 
 __device__ __forceinline__ int class_of(long lab) { return lab >= 0 && lab < DAD_C ? (int)lab : -1; }
-__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
 }  // namespace
 
@@ -199,18 +196,9 @@ __global__ __launch_bounds__(kThreads, 2) void dad_cluster_pair(ClusterPairArgs 
   __shared__ __attribute__((aligned(16))) float bt[kTile * kLd];
   __shared__ float nj_s[kTile], ni_s[kTile];
   __shared__ int lj_s[kTile];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int kh = lane >> 5, l32 = lane & 31;
-  const int rh = w >> 1, ch = w & 1;
-  const int n = a.n;
+  const int tid = threadIdx.x;
+  const GramLane g = dad_gram_lane(tid);
   const int i0 = kTile * (int)blockIdx.x, chunk = blockIdx.y;
-
-  // A operand: row i0 + 32 rh + l32; MFMA step e of k-block q takes k = 8 q + 4 kh + e on both operands
-  f32x4 av[DAD_H / 8];
-  dad_gram_load_a(av, a.emb, a.mean, i0 + 32 * rh + l32, n, kh);
-  const f32x4 mu4 = *reinterpret_cast<const f32x4*>(a.mean + 4 * (tid & 63));   // the columns this thread stages
-  if (tid < kTile) ni_s[tid] = a.norms[i0 + tid];
   float bins[16][DAD_C];
 #pragma unroll
   for (int r = 0; r < 16; ++r)
@@ -218,29 +206,15 @@ __global__ __launch_bounds__(kThreads, 2) void dad_cluster_pair(ClusterPairArgs 
     for (int c = 0; c < DAD_C; ++c) bins[r][c] = 0.0f;
 
   const int t_end = (chunk + 1) * a.per < a.ct ? (chunk + 1) * a.per : a.ct;
-  for (int t = chunk * a.per; t < t_end; ++t) {
-    const int j0 = kTile * t;
-    __syncthreads();      // the previous tile's operand reads are done
-    dad_gram_stage(bt, a.emb, mu4, j0, n, tid);
-    if (tid < kTile) {
-      const int j = j0 + tid;
-      nj_s[tid] = j < n ? a.norms[j] : 0.0f;
-      lj_s[tid] = j < n ? class_of(a.labels[j]) : -1;
-    }
-    __syncthreads();
-    const int jc = 32 * ch + l32;
-    const f32x16 acc = dad_gram_block(av, bt, jc, kh);
-    const int cj = lj_s[jc], jg = j0 + jc;
-    const float nj = nj_s[jc];
+  dad_gram_walk(
+      a.emb, a.norms, a.mean, a.n, i0, chunk * a.per, t_end, 1, bt, nj_s, ni_s,
+      [&](int c, int j) { lj_s[c] = j < a.n ? class_of(a.labels[j]) : -1; },
+      [&](int r, int, int jc, int, float d2) {
+        const int cj = lj_s[jc];
+        const float d = sqrtf(d2);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int il = 32 * rh + dad_acc_row(r, kh);
-      float d = sqrtf(fmaxf((ni_s[il] + nj) - 2.0f * acc[r], 0.0f));
-      d = i0 + il == jg ? 0.0f : d;
-#pragma unroll
-      for (int c = 0; c < DAD_C; ++c) bins[r][c] += cj == c ? d : 0.0f;
-    }
-  }
+        for (int c = 0; c < DAD_C; ++c) bins[r][c] += cj == c ? d : 0.0f;
+      });
   // the 32 columns of a lane half -> lane l32 = 0, by a fixed tree
 #pragma unroll
   for (int r = 0; r < 16; ++r)
@@ -252,11 +226,11 @@ __global__ __launch_bounds__(kThreads, 2) void dad_cluster_pair(ClusterPairArgs 
       bins[r][c] = v;
     }
   __syncthreads();        // the last tile's operand reads are done: bt becomes red[2][64][4]
-  if (l32 == 0) {
+  if (g.l32 == 0) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int il = 32 * rh + dad_acc_row(r, kh);
-      *reinterpret_cast<f32x4*>(&bt[(ch * kTile + il) * DAD_C]) = f32x4{bins[r][0], bins[r][1], bins[r][2], bins[r][3]};
+      const int il = 32 * g.rh + dad_acc_row(r, g.kh);
+      *reinterpret_cast<f32x4*>(&bt[(g.ch * kTile + il) * DAD_C]) = f32x4{bins[r][0], bins[r][1], bins[r][2], bins[r][3]};
     }
   }
   __syncthreads();
@@ -381,8 +355,6 @@ __global__ __launch_bounds__(64) void dad_cluster_final(const double* __restrict
   }
 }
 
-#define CM_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
 extern "C" int dad_cluster_plan(int64_t n, int cus, int* row_tiles, int* chunks, int* tiles_per_chunk) {
   if (!row_tiles || !chunks || !tiles_per_chunk) return DAD_E_ARG;
   if (n < 1 || n > DAD_CM_MAX_N || cus < 1) return DAD_E_SHAPE;
@@ -390,13 +362,10 @@ extern "C" int dad_cluster_plan(int64_t n, int cus, int* row_tiles, int* chunks,
   // resident at once (rounding up instead left 5,531 rows on 256 CUs a second round of 10 workgroups as
   // long as the first of 512)
   const int rt = (int)((n + kTile - 1) / kTile);
-  int want = 2 * cus / rt;
-  const int cap = rt < kMaxChunks ? rt : kMaxChunks;
-  want = want < 1 ? 1 : (want > cap ? cap : want);
-  const int per = (rt + want - 1) / want;
-  *row_tiles = rt;
-  *tiles_per_chunk = per;
-  *chunks = (rt + per - 1) / per;        // (no empty chunk)
+  const PairPlan p = pair_plan(n, 2 * cus / rt, kMaxChunks);
+  *row_tiles = p.rt;
+  *chunks = p.chunks;
+  *tiles_per_chunk = p.per;
   return DAD_OK;
 }
 
@@ -406,55 +375,37 @@ extern "C" size_t dad_cluster_workspace_bytes(int64_t n) {
 }
 
 extern "C" int dad_cluster_metrics_chunked(const float* emb, const int64_t* labels, int64_t n, double* out, float* sil,
-                                           int chunks, void* workspace, void* stream_) {
-  if (!emb || !labels || !out || !workspace) return DAD_E_ARG;
+                                           int chunks, void* ws, void* stream_) {
+  if (!emb || !labels || !out || !ws) return DAD_E_ARG;
   if (n < 1 || n > DAD_CM_MAX_N) return DAD_E_SHAPE;
-  int rt = 0, nch = 0, per = 0;
-  if (chunks <= 0) {
-    int cus = 0;
-    const int rc = device_cus(&cus);
-    if (rc) return rc;
-    const int pr = dad_cluster_plan(n, cus, &rt, &nch, &per);
-    if (pr) return pr;
-  } else {
-    rt = (int)((n + kTile - 1) / kTile);
-    const int cap = rt < kMaxChunks ? rt : kMaxChunks;
-    const int want = chunks > cap ? cap : chunks;
-    per = (rt + want - 1) / want;
-    nch = (rt + per - 1) / per;
-  }
+  PairPlan pl;
+  DAD_RET(pair_resolve(n, chunks, kMaxChunks, dad_cluster_plan, &pl));
+  const int rt = pl.rt;
   hipStream_t stream = (hipStream_t)stream_;
   const ClusterWs L = cluster_ws_layout(n);
-  char* ws = (char*)workspace;
-  float* norms = (float*)(ws + L.norms);
-  float* part = (float*)(ws + L.part);
-  double* csum = (double*)(ws + L.csum);
-  int32_t* cnt = (int32_t*)(ws + L.cnt);
-  double* cent = (double*)(ws + L.cent);
-  float* mean = (float*)(ws + L.mean);
-  int32_t* hdr_i = (int32_t*)(ws + L.hdr_i);
-  double* hdr_d = (double*)(ws + L.hdr_d);
-  double* wpart = (double*)(ws + L.wpart);
-  double* silpart = (double*)(ws + L.silpart);
+  float *norms = ws_ptr<float>(ws, L.norms), *part = ws_ptr<float>(ws, L.part), *mean = ws_ptr<float>(ws, L.mean);
+  double *csum = ws_ptr<double>(ws, L.csum), *cent = ws_ptr<double>(ws, L.cent), *hdr_d = ws_ptr<double>(ws, L.hdr_d);
+  double *wpart = ws_ptr<double>(ws, L.wpart), *silpart = ws_ptr<double>(ws, L.silpart);
+  int32_t *cnt = ws_ptr<int32_t>(ws, L.cnt), *hdr_i = ws_ptr<int32_t>(ws, L.hdr_i);
 
   hipLaunchKernelGGL(dad_cluster_prep, dim3(rt), dim3(kThreads), 0, stream, emb, labels, (int)n, csum, cnt);
-  CM_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   hipLaunchKernelGGL(dad_cluster_stats, dim3(1), dim3(kThreads), 0, stream, csum, cnt, rt, cent, mean, hdr_i, hdr_d);
-  CM_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   hipLaunchKernelGGL(dad_cluster_norms, dim3(rt), dim3(128), 0, stream, emb, mean, (int)n, norms);
-  CM_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   ClusterPairArgs pa;
   pa.emb = emb; pa.labels = labels; pa.norms = norms; pa.mean = mean; pa.part = part;
-  pa.n = (int)n; pa.npad = rt * kTile; pa.ct = rt; pa.per = per;
-  hipLaunchKernelGGL(dad_cluster_pair, dim3(rt, nch), dim3(kThreads), 0, stream, pa);
-  CM_TRY(hipGetLastError());
+  pa.n = (int)n; pa.npad = rt * kTile; pa.ct = rt; pa.per = pl.per;
+  hipLaunchKernelGGL(dad_cluster_pair, dim3(rt, pl.chunks), dim3(kThreads), 0, stream, pa);
+  DAD_TRY(hipGetLastError());
   ClusterRowArgs ra;
   ra.emb = emb; ra.labels = labels; ra.part = part; ra.cent = cent; ra.hdr_i = hdr_i; ra.sil = sil;
-  ra.wpart = wpart; ra.silpart = silpart; ra.n = (int)n; ra.npad = rt * kTile; ra.chunks = nch;
+  ra.wpart = wpart; ra.silpart = silpart; ra.n = (int)n; ra.npad = rt * kTile; ra.chunks = pl.chunks;
   hipLaunchKernelGGL(dad_cluster_rows, dim3(rt), dim3(kThreads), 0, stream, ra);
-  CM_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   hipLaunchKernelGGL(dad_cluster_final, dim3(1), dim3(64), 0, stream, wpart, silpart, hdr_i, hdr_d, rt, out);
-  CM_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   return DAD_OK;
 }
 

@@ -517,6 +517,27 @@ struct DadWs {
 
 static inline size_t dad_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// Host helpers of every unit of the C ABI, the ones outside the step included: leave the function with a HIP error
+// or with a non-zero DAD_* code, and carve a workspace by a layout's byte offsets.
+#define DAD_TRY(expr)                           \
+  do {                                          \
+    hipError_t e_ = (expr);                     \
+    if (e_ != hipSuccess) return (int)e_;       \
+  } while (0)
+#define DAD_RET(expr)        \
+  do {                       \
+    const int rc_ = (expr);  \
+    if (rc_) return rc_;     \
+  } while (0)
+
+template <typename T>
+inline T* ws_ptr(void* ws, size_t off) {
+  return reinterpret_cast<T*>(reinterpret_cast<char*>(ws) + off);
+}
+
+// compute units of the current device (cached per device; dad_abi.hip)
+int device_cus(int* out);
+
 // weight-gradient split-K factor.  FP32 (dad_wgrad_f32, 6 column blocks per split): 42
 // splits -> 252 tiles.  FP16/BF16 (dad_wgrad_direct, 12 column blocks per split): 21 splits -> 252 workgroups,
 // one per CU, and never more than WGD_MAXU = 64 slabs per split (its dL/de table in LDS).

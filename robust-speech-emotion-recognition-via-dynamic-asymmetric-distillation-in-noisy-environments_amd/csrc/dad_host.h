@@ -1,22 +1,7 @@
-// Host helpers shared by the translation units of the C ABI (dad_abi.hip, encoder_ops.hip).
+// Host helpers shared by the step's translation units of the C ABI (dad_abi.hip, encoder_ops.hip); DAD_TRY, DAD_RET,
+// ws_ptr and device_cus, which the units outside the step use too, come from dad_common.h.
 #pragma once
 #include "step_plan.h"
-
-#define DAD_TRY(expr)                           \
-  do {                                          \
-    hipError_t e_ = (expr);                     \
-    if (e_ != hipSuccess) return (int)e_;       \
-  } while (0)
-#define DAD_RET(expr)        \
-  do {                       \
-    const int rc_ = (expr);  \
-    if (rc_) return rc_;     \
-  } while (0)
-
-template <typename T>
-inline T* ws_ptr(void* ws, size_t off) {
-  return reinterpret_cast<T*>(reinterpret_cast<char*>(ws) + off);
-}
 
 struct Keys {
   uint32_t weak, strong, feat, tstart, drop1, drop2;
@@ -32,9 +17,6 @@ inline Keys keys_of(const dad_config* c) {
   k.drop2 = dad_stream_key(c->seed, c->counter, DAD_RNG_DROP2);
   return k;
 }
-
-// compute units of the current device (cached per device)
-int device_cus(int* out);
 
 // The KernelSig (step_plan.h) of a list of argument blocks; no other list can be launched.
 template <typename... A> struct SigOf;

@@ -456,8 +456,6 @@ void launch_encode(const EvalEncArgs& ea, bool teach, bool f16, hipStream_t stre
 
 }  // namespace
 
-#define EV_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
 extern "C" size_t dad_eval_workspace_bytes(int64_t n, int64_t slabs, int precision, int with_teacher) {
   if (!eval_shape_ok(n, slabs)) return 0;
   return eval_ws_layout(n, slabs, precision, with_teacher ? 1 : 0).bytes;
@@ -489,14 +487,14 @@ extern "C" int dad_eval_split(const dad_eval_args* args, void* workspace, void* 
     if (f16) {
       hipLaunchKernelGGL(dad_eval_w1h, dim3((DAD_H * DAD_D + 255) / 256, teach ? 2 : 1), dim3(256), 0, stream,
                          args->student, args->teacher, (uint16_t*)(ws + L.w1h_s), (uint16_t*)(ws + L.w1h_t));
-      EV_TRY(hipGetLastError());
+      DAD_TRY(hipGetLastError());
     }
     switch (dt) {
       case DAD_STORE_F16: launch_encode<DAD_STORE_F16>(ea, teach, f16, stream); break;
       case DAD_STORE_BF16: launch_encode<DAD_STORE_BF16>(ea, teach, f16, stream); break;
       default: launch_encode<DAD_STORE_F32>(ea, teach, f16, stream); break;
     }
-    EV_TRY(hipGetLastError());
+    DAD_TRY(hipGetLastError());
   }
 
   EvalHeadArgs ha;
@@ -511,7 +509,7 @@ extern "C" int dad_eval_split(const dad_eval_args* args, void* workspace, void* 
   ha.ws_score = (float*)(ws + L.score); ha.ws_bad = (int32_t*)(ws + L.bad);
   hipLaunchKernelGGL(dad_eval_head, dim3((unsigned)((ea.n + kHeadWaves - 1) / kHeadWaves)), dim3(64 * kHeadWaves), 0,
                      stream, ha);
-  EV_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
 
   EvalResArgs ra;
   memset(&ra, 0, sizeof(ra));
@@ -519,6 +517,6 @@ extern "C" int dad_eval_split(const dad_eval_args* args, void* workspace, void* 
   ra.pred_s = ha.ws_pred_s; ra.pred_t = ha.ws_pred_t; ra.score = ha.ws_score; ra.bad = ha.ws_bad;
   ra.counts = args->counts; ra.moments = args->moments;
   hipLaunchKernelGGL(dad_eval_result, dim3(1), dim3(kResThreads), 0, stream, ra);
-  EV_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   return DAD_OK;
 }

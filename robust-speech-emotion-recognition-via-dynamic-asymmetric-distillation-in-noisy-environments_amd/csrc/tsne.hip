@@ -8,7 +8,7 @@
 //                         non-finite component
 //     dad_tsne_mean       one workgroup: the tiles in tile order -> the rows' mean rounded to fp32, the count
 //     dad_cluster_norms   (cluster.hip) |x_i - mu|^2 as the diagonal of the Gram block
-//     dad_tsne_dist       the Gram block of cluster_gram.h per 64 x 64 tile -> D_ij = max(|a_i|^2 + |a_j|^2 - 2 a_i.a_j, 0)
+//     dad_tsne_dist       pairwise.h's walk of the Gram block per 64 x 64 tile -> D_ij = dad_pair_d2
 //                         into P (D_ii = 0; a duplicate row's distance is exactly 0)
 //     dad_tsne_search     one wave per row: scikit-learn's _binary_search_perplexity in double on the row's fp32
 //                         distances; the row's conditional probabilities replace its distances
@@ -32,10 +32,8 @@
 #include <cmath>
 #include <cstdint>
 
-#include "cluster_gram.h"
 #include "dad_common.h"
-
-int device_cus(int* out);   // dad_abi.hip
+#include "pairwise.h"
 
 namespace {
 
@@ -83,8 +81,6 @@ TsneWs tsne_ws_layout(int64_t n) {
   w.bytes = off;
   return w;
 }
-
-__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
 // the sum of v over the workgroup's kStepThreads threads in a fixed order (each wave's fixed DPP tree, then the waves
 // in wave order); every thread gets it
@@ -146,32 +142,11 @@ __global__ __launch_bounds__(kThreads, 2) void dad_tsne_dist(const float* __rest
                                                              float* __restrict__ P) {
   __shared__ __attribute__((aligned(16))) float bt[kTile * kGramLd];
   __shared__ float nj_s[kTile], ni_s[kTile];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int kh = lane >> 5, l32 = lane & 31;
-  const int rh = w >> 1, ch = w & 1;
-  const int i0 = kTile * (int)blockIdx.x;
-  f32x4 av[DAD_H / 8];
-  dad_gram_load_a(av, emb, mean, i0 + 32 * rh + l32, n, kh);
-  const f32x4 mu4 = *reinterpret_cast<const f32x4*>(mean + 4 * (tid & 63));
-  if (tid < kTile) ni_s[tid] = norms[i0 + tid];
-  for (int t = blockIdx.y; t < ct; t += gridDim.y) {
-    const int j0 = kTile * t;
-    __syncthreads();      // the previous tile's operand reads are done
-    dad_gram_stage(bt, emb, mu4, j0, n, tid);
-    if (tid < kTile) nj_s[tid] = norms[j0 + tid];
-    __syncthreads();
-    const int jc = 32 * ch + l32, jg = j0 + jc;
-    const f32x16 acc = dad_gram_block(av, bt, jc, kh);
-    const float nj = nj_s[jc];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int il = 32 * rh + dad_acc_row(r, kh), ig = i0 + il;
-      float d = fmaxf((ni_s[il] + nj) - 2.0f * acc[r], 0.0f);
-      d = ig == jg ? 0.0f : d;
-      if (ig < n && jg < n) P[(size_t)ig * ld + jg] = d;
-    }
-  }
+  dad_gram_walk(
+      emb, norms, mean, n, kTile * (int)blockIdx.x, blockIdx.y, ct, gridDim.y, bt, nj_s, ni_s, [](int, int) {},
+      [&](int, int ig, int, int jg, float d2) {
+        if (ig < n && jg < n) P[(size_t)ig * ld + jg] = d2;
+      });
 }
 
 // _binary_search_perplexity of one row per wave.  The row of P holds D_i. on entry and the conditional c_i. on exit.
@@ -497,36 +472,12 @@ __global__ __launch_bounds__(kStepThreads) void dad_tsne_init(RunHdr* hdr, float
   }
 }
 
-#define TS_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
 namespace {
 
-struct TsnePlan { int rt, chunks, per; };
-
-void plan_for(int64_t n, int want, TsnePlan* p) {
-  const int rt = (int)((n + kTile - 1) / kTile);
-  const int cap = rt < kMaxChunks ? rt : kMaxChunks;
-  want = want < 1 ? 1 : (want > cap ? cap : want);
-  p->rt = rt;
-  p->per = (rt + want - 1) / want;
-  p->chunks = (rt + p->per - 1) / p->per;      // (no empty chunk)
-}
-
-int resolve_plan(int64_t n, int chunks, TsnePlan* p) {
-  if (chunks > 0) {
-    plan_for(n, chunks, p);
-    return DAD_OK;
-  }
-  int cus = 0;
-  const int rc = device_cus(&cus);
-  if (rc) return rc;
-  return dad_tsne_plan(n, cus, &p->rt, &p->chunks, &p->per);
-}
-
-int launch_force(const float* P, const float* Y, int64_t n, const TsnePlan& pl, const TsneWs& L, char* ws, bool kl,
+int launch_force(const float* P, const float* Y, int64_t n, const PairPlan& pl, const TsneWs& L, void* ws, bool kl,
                  const int32_t* stop, hipStream_t stream) {
   TsneForceArgs fa;
-  fa.P = P; fa.Y = Y; fa.part = (float*)(ws + L.part); fa.partd = (double*)(ws + L.partd); fa.stop = stop;
+  fa.P = P; fa.Y = Y; fa.part = ws_ptr<float>(ws, L.part); fa.partd = ws_ptr<double>(ws, L.partd); fa.stop = stop;
   fa.n = (int)n; fa.npad = pl.rt * kTile; fa.ld = pl.rt * kTile; fa.per = pl.per;
   if (kl) hipLaunchKernelGGL(dad_tsne_force<true>, dim3(pl.rt, pl.chunks), dim3(kThreads), 0, stream, fa);
   else hipLaunchKernelGGL(dad_tsne_force<false>, dim3(pl.rt, pl.chunks), dim3(kThreads), 0, stream, fa);
@@ -541,10 +492,9 @@ extern "C" int dad_tsne_plan(int64_t n, int cus, int* row_tiles, int* chunks, in
   // the force kernel keeps 41 registers and 20 KB of LDS: four workgroups of 256 threads a CU hide the latency of
   // the P reads; a chunk shorter than 4 column tiles (64 columns a wave) is mostly prologue, and every chunk adds
   // 5 n partial sums for the single workgroup of the step launch to read
-  TsnePlan p;
   const int rt = (int)((n + kTile - 1) / kTile);
   const int want = 4 * cus / rt;
-  plan_for(n, want < rt / 4 ? want : rt / 4, &p);
+  const PairPlan p = pair_plan(n, want < rt / 4 ? want : rt / 4, kMaxChunks);
   *row_tiles = p.rt;
   *chunks = p.chunks;
   *tiles_per_chunk = p.per;
@@ -557,62 +507,55 @@ extern "C" size_t dad_tsne_workspace_bytes(int64_t n) {
 }
 
 extern "C" int dad_tsne_affinities(const float* emb, int64_t n, double perplexity, float* P, double* beta,
-                                   void* workspace, void* stream_) {
-  if (!emb || !P || !workspace) return DAD_E_ARG;
+                                   void* ws, void* stream_) {
+  if (!emb || !P || !ws) return DAD_E_ARG;
   if (n < 2 || n > DAD_TS_MAX_N) return DAD_E_SHAPE;
   if (!(perplexity > 0.0) || !(perplexity < (double)n)) return DAD_E_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   const TsneWs L = tsne_ws_layout(n);
-  char* ws = (char*)workspace;
   const int rt = (int)((n + kTile - 1) / kTile), ld = rt * kTile;
-  float* mean = (float*)(ws + L.mean);
-  float* norms = (float*)(ws + L.norms);
-  double* csum = (double*)(ws + L.csum);
-  int32_t* bad = (int32_t*)(ws + L.bad);
-  double* tsum = (double*)(ws + L.tsum);
-  double* total = (double*)(ws + L.total);
+  float *mean = ws_ptr<float>(ws, L.mean), *norms = ws_ptr<float>(ws, L.norms);
+  double *csum = ws_ptr<double>(ws, L.csum), *tsum = ws_ptr<double>(ws, L.tsum), *total = ws_ptr<double>(ws, L.total);
+  int32_t* bad = ws_ptr<int32_t>(ws, L.bad);
 
   hipLaunchKernelGGL(dad_tsne_colsum, dim3(rt), dim3(kThreads), 0, stream, emb, (int)n, csum, bad);
-  TS_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dad_tsne_mean, dim3(1), dim3(kThreads), 0, stream, csum, bad, rt, (int)n, mean, (int32_t*)(ws + L.hdr));
-  TS_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
+  hipLaunchKernelGGL(dad_tsne_mean, dim3(1), dim3(kThreads), 0, stream, csum, bad, rt, (int)n, mean, ws_ptr<int32_t>(ws, L.hdr));
+  DAD_TRY(hipGetLastError());
   hipLaunchKernelGGL(dad_cluster_norms, dim3(rt), dim3(128), 0, stream, emb, mean, (int)n, norms);
-  TS_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   hipLaunchKernelGGL(dad_tsne_dist, dim3(rt, rt < 8 ? rt : 8), dim3(kThreads), 0, stream, emb, norms, mean, (int)n, rt, ld, P);
-  TS_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   // (the perplexity as the C float scikit-learn's search receives it)
   hipLaunchKernelGGL(dad_tsne_search, dim3((unsigned)((n + 3) / 4)), dim3(kThreads), 0, stream, P, (int)n, ld,
                      log((double)(float)perplexity), beta);
-  TS_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   hipLaunchKernelGGL(dad_tsne_sym, dim3(rt, rt), dim3(kThreads), 0, stream, P, (int)n, ld, rt, tsum);
-  TS_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   hipLaunchKernelGGL(dad_tsne_total, dim3(1), dim3(kThreads), 0, stream, tsum, rt, total);
-  TS_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   hipLaunchKernelGGL(dad_tsne_scale, dim3((unsigned)n), dim3(kThreads), 0, stream, P, (int)n, ld, total);
-  TS_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   return DAD_OK;
 }
 
 extern "C" int dad_tsne_gradient_chunked(const float* P, int64_t n, const float* Y, double exaggeration, double* out,
-                                         float* grad, int chunks, void* workspace, void* stream_) {
-  if (!P || !Y || !out || !grad || !workspace) return DAD_E_ARG;
+                                         float* grad, int chunks, void* ws, void* stream_) {
+  if (!P || !Y || !out || !grad || !ws) return DAD_E_ARG;
   if (n < 2 || n > DAD_TS_MAX_N) return DAD_E_SHAPE;
   if (!(exaggeration > 0.0)) return DAD_E_ARG;
-  TsnePlan pl;
-  const int rc = resolve_plan(n, chunks, &pl);
-  if (rc) return rc;
+  PairPlan pl;
+  DAD_RET(pair_resolve(n, chunks, kMaxChunks, dad_tsne_plan, &pl));
   hipStream_t stream = (hipStream_t)stream_;
   const TsneWs L = tsne_ws_layout(n);
-  char* ws = (char*)workspace;
-  const int fr = launch_force(P, Y, n, pl, L, ws, true, nullptr, stream);
-  if (fr) return fr;
+  DAD_RET(launch_force(P, Y, n, pl, L, ws, true, nullptr, stream));
   TsneStepArgs sa = {};
-  sa.part = (const float*)(ws + L.part); sa.partd = (const double*)(ws + L.partd);
+  sa.part = ws_ptr<float>(ws, L.part); sa.partd = ws_ptr<double>(ws, L.partd);
   sa.grad = grad; sa.out = out;
   sa.n = (int)n; sa.npad = pl.rt * kTile; sa.chunks = pl.chunks;
   sa.compute = 1; sa.ex = (float)exaggeration;
   hipLaunchKernelGGL(dad_tsne_step<false>, dim3(1), dim3(kStepThreads), 0, stream, sa);
-  TS_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   return DAD_OK;
 }
 
@@ -622,22 +565,20 @@ extern "C" int dad_tsne_gradient(const float* P, int64_t n, const float* Y, doub
 }
 
 extern "C" int dad_tsne_run(const float* P, int64_t n, float* Y, const dad_tsne_args* args, double* history,
-                            double* out, void* workspace, void* stream_) {
-  if (!P || !Y || !args || !history || !out || !workspace) return DAD_E_ARG;
+                            double* out, void* ws, void* stream_) {
+  if (!P || !Y || !args || !history || !out || !ws) return DAD_E_ARG;
   if (n < 2 || n > DAD_TS_MAX_N) return DAD_E_SHAPE;
   if (args->max_iter < 1 || args->n_iter_without_progress < 0 || !(args->early_exaggeration > 0.0) ||
       !(args->learning_rate > 0.0))
     return DAD_E_ARG;
-  TsnePlan pl;
-  const int rc = resolve_plan(n, 0, &pl);
-  if (rc) return rc;
+  PairPlan pl;
+  DAD_RET(pair_resolve(n, 0, kMaxChunks, dad_tsne_plan, &pl));
   hipStream_t stream = (hipStream_t)stream_;
   const TsneWs L = tsne_ws_layout(n);
-  char* ws = (char*)workspace;
-  RunHdr* hdr = (RunHdr*)(ws + L.hdr + 64);
+  RunHdr* hdr = ws_ptr<RunHdr>(ws, L.hdr + 64);
   TsneStepArgs sa = {};
-  sa.part = (const float*)(ws + L.part); sa.partd = (const double*)(ws + L.partd);
-  sa.Y = Y; sa.upd = (float*)(ws + L.upd); sa.gains = (float*)(ws + L.gains);
+  sa.part = ws_ptr<float>(ws, L.part); sa.partd = ws_ptr<double>(ws, L.partd);
+  sa.Y = Y; sa.upd = ws_ptr<float>(ws, L.upd); sa.gains = ws_ptr<float>(ws, L.gains);
   sa.hdr = hdr; sa.history = history; sa.out = out;
   sa.n = (int)n; sa.npad = pl.rt * kTile; sa.chunks = pl.chunks;
   sa.max_iter = args->max_iter;
@@ -646,15 +587,14 @@ extern "C" int dad_tsne_run(const float* P, int64_t n, float* Y, const dad_tsne_
   sa.lr = (float)args->learning_rate; sa.early_ex = (float)args->early_exaggeration; sa.ex = 1.0f;
   sa.min_grad_norm = args->min_grad_norm;
   hipLaunchKernelGGL(dad_tsne_init, dim3(1), dim3(kStepThreads), 0, stream, hdr, sa.upd, sa.gains, out, (int)n);
-  TS_TRY(hipGetLastError());
+  DAD_TRY(hipGetLastError());
   for (int it = 0; it < args->max_iter; ++it) {
     sa.it = it;
     sa.check = (it + 1) % kCheck == 0;
     sa.compute = sa.check || it == sa.explore_n - 1 || it == args->max_iter - 1;
-    const int fr = launch_force(P, Y, n, pl, L, ws, sa.compute != 0, &hdr->stop, stream);
-    if (fr) return fr;
+    DAD_RET(launch_force(P, Y, n, pl, L, ws, sa.compute != 0, &hdr->stop, stream));
     hipLaunchKernelGGL(dad_tsne_step<true>, dim3(1), dim3(kStepThreads), 0, stream, sa);
-    TS_TRY(hipGetLastError());
+    DAD_TRY(hipGetLastError());
   }
   return DAD_OK;
 }

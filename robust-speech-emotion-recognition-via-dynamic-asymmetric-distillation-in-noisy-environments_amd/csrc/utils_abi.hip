@@ -19,12 +19,6 @@
 
 namespace {
 
-#define DAD_TRY(expr)                           \
-  do {                                          \
-    hipError_t e_ = (expr);                     \
-    if (e_ != hipSuccess) return (int)e_;       \
-  } while (0)
-
 struct AugArgs {
   const float* x; float* out;
   uint64_t n;                 // B * T * D elements

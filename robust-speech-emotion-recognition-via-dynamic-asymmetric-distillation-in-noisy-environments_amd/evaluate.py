@@ -380,12 +380,35 @@ def calibrate_anchors_store(model, clean, noisy, num_classes=4, anchor_std_k=1.5
     return base * shift
 
 
+def _enqueue_embeddings(model, plan, use_teacher, precision):
+    """enqueue_eval_split for the split's embeddings alone (the teacher's with use_teacher): the device tensor."""
+    name = "t_emb" if use_teacher else "emb"
+    return enqueue_eval_split(model, plan, use_teacher=use_teacher, precision=precision, outputs=(name,))[name]
+
+
 def embed_store(model, store_or_loader, use_teacher=False):
     """Eval-mode embeddings [n, 256] of every utterance of the split, in the store's sample order
     (the split-wide use of SSRLModel.get_embeddings, I/model.py:247-265), on the device."""
     model.eval()
-    name = "t_emb" if use_teacher else "emb"
-    return evaluate_store(model, store_or_loader, use_teacher=use_teacher, outputs=(name,))[name]
+    plan = EvalPlan.of(store_or_loader)
+    emb = _enqueue_embeddings(model, plan, use_teacher, "fp32")
+    _read_eval_block(plan, {})              # (raises on a non-finite logit, as evaluate_store does)
+    return emb
+
+
+def _check_emb(emb):
+    if not torch.is_tensor(emb) or not emb.is_cuda or emb.dtype != torch.float32 or emb.dim() != 2 \
+            or emb.shape[1] != 256:
+        raise ValueError("emb must be a float32 device tensor [n, 256]")
+    return emb.contiguous()
+
+
+def _workspace(symbol, feature, n, lo, hi, device):
+    need = int(_lib.require(symbol, feature)(int(n)))
+    if need == 0:           # (the library's answer for n outside [lo, hi])
+        takes = "t-SNE takes" if feature == "tsne" else "cluster metrics take"
+        raise ValueError("%s %d <= n <= %d rows, got %d" % (takes, lo, hi, n))
+    return torch.empty(need, dtype=torch.uint8, device=device)
 
 
 # ------------------------------------------------------------------ class separation of a split
@@ -395,11 +418,7 @@ def embed_store(model, store_or_loader, use_teacher=False):
 # dad_eval_split leaves there; one copy of 16 doubles returns them.
 
 def _cluster_workspace(n, device):
-    fn = _lib.require("dad_cluster_workspace_bytes", "cluster_metrics")
-    need = int(fn(int(n)))
-    if need == 0:
-        raise ValueError("cluster metrics take 1 <= n <= %d rows, got %d" % (_lib.CM_MAX_N, n))
-    return torch.empty(need, dtype=torch.uint8, device=device)
+    return _workspace("dad_cluster_workspace_bytes", "cluster_metrics", n, 1, _lib.CM_MAX_N, device)
 
 
 def _enqueue_cluster(emb, labels, block, sil, ws, chunks=0):
@@ -450,10 +469,7 @@ def cluster_metrics(emb, labels, samples=False, _chunks=0):
     'silhouette_samples' [n] (0 for an unlabelled row).  Where scikit-learn would raise (fewer than 2
     classes present, or as many classes as labelled rows) both scores are 0.0, 'valid' is False and a
     RuntimeWarning is issued.  Raises DadError when a labelled row has a non-finite component."""
-    if not torch.is_tensor(emb) or not emb.is_cuda or emb.dtype != torch.float32 or emb.dim() != 2 \
-            or emb.shape[1] != 256:
-        raise ValueError("emb must be a float32 device tensor [n, 256]")
-    emb = emb.contiguous()
+    emb = _check_emb(emb)
     labels = torch.as_tensor(labels).to(device=emb.device, dtype=torch.int64).contiguous()
     if labels.shape != (emb.shape[0],):
         raise ValueError("labels must be [n]")
@@ -474,8 +490,7 @@ def enqueue_cluster_metrics_store(model, plan, use_teacher=False, precision="fp3
     plan's device labels.  The block lands in plan.cluster_buffers()[1].  Returns (emb, sil or None)."""
     if plan.labels_d is None:
         raise ValueError("the split has no labels")
-    name = "t_emb" if use_teacher else "emb"
-    emb = enqueue_eval_split(model, plan, use_teacher=use_teacher, precision=precision, outputs=(name,))[name]
+    emb = _enqueue_embeddings(model, plan, use_teacher, precision)
     ws, block_d, _ = plan.cluster_buffers()
     sil = torch.empty(plan.n, dtype=torch.float32, device=plan.device) if samples else None
     _enqueue_cluster(emb, plan.labels_d, block_d, sil, ws)
@@ -526,18 +541,7 @@ def separation_report(initial_model, trained_model, store_or_loader):
 # descent, which the host only enqueues.
 
 def _tsne_workspace(n, device):
-    fn = _lib.require("dad_tsne_workspace_bytes", "tsne")
-    need = int(fn(int(n)))
-    if need == 0:
-        raise ValueError("t-SNE takes 2 <= n <= %d rows, got %d" % (_lib.TS_MAX_N, n))
-    return torch.empty(need, dtype=torch.uint8, device=device)
-
-
-def _check_emb(emb):
-    if not torch.is_tensor(emb) or not emb.is_cuda or emb.dtype != torch.float32 or emb.dim() != 2 \
-            or emb.shape[1] != 256:
-        raise ValueError("emb must be a float32 device tensor [n, 256]")
-    return emb.contiguous()
+    return _workspace("dad_tsne_workspace_bytes", "tsne", n, 2, _lib.TS_MAX_N, device)
 
 
 def _check_p(P):
@@ -669,9 +673,7 @@ def tsne_store(model, store_or_loader, use_teacher=False, precision="fp32", **ts
     device: the embeddings never reach the host."""
     model.eval()
     plan = EvalPlan.of(store_or_loader)
-    name = "t_emb" if use_teacher else "emb"
-    emb = enqueue_eval_split(model, plan, use_teacher=use_teacher, precision=precision, outputs=(name,))[name]
-    return tsne(emb, **tsne_args)
+    return tsne(_enqueue_embeddings(model, plan, use_teacher, precision), **tsne_args)
 
 
 def tsne_report(initial_model, trained_model, store_or_loader, **tsne_args):

@@ -33,6 +33,7 @@ def main():
         subprocess.run([_build.HIPCC] + _build.CFLAGS + extra + ["-c", os.path.join(tmp, s), "-o", o], check=True)
         objs.append(o)
     out = _build.lib_path(name)
+    os.makedirs(os.path.dirname(out), exist_ok=True)      # (a checkout that has not been built yet has no lib/)
     subprocess.run([_build.HIPCC, "-shared", "-o", out] + objs + ["-L" + os.path.join(_build.ROCM, "lib"), "-lrccl"],
                    check=True)
     print("built", out, "from", rev)
