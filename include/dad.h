@@ -624,6 +624,79 @@ typedef struct dad_tsne_args {
 int dad_tsne_run(const float* P, int64_t n, float* Y, const dad_tsne_args* args, double* history, double* out,
                  void* workspace, void* stream);
 
+/* --- the clean-noisy domain gap of two splits' embeddings (csrc/domain_gap.hip) -----------
+ * ECDALoss (I/utils.py:510-652) on whole splits instead of one batch.  emb [n][256] holds the rows of both domains
+ * (dad_eval_split's emb of two splits, concatenated in any order), labels [n] their classes, domain [n] 0 for a
+ * source / clean row and non-zero for a target / noisy one, weights [n] the rows' sample weights (NULL: all ones).
+ * A row with a label outside [0, 4) takes no part in anything (how a caller applies a DACP mask); it and the rows
+ * past n are left out by selection, so their values, NaN included, reach no sum.
+ *
+ * For a set S of m rows with D_ij = |x_i - x_j|^2:  bw = sum_ij D_ij / (m^2 - m) / 4 (0 for m < 2),
+ * K_ij = sum_{b = 0 .. 4} exp(-D_ij / (bw 2^b + 1e-8))  (kernel_num = 5, kernel_mul = 2),
+ * term_ss = sum_{i, j in src} w_i w_j K_ij / ((sum_src w)^2 + 1e-8), term_tt and term_st likewise (st: i in src, j in
+ * tgt; the diagonal included), mmd = (ss + tt) - 2 st.
+ * Per class c: S = the class's rows of both domains with their weights; gate_c = (n_src,c >= 2 and n_tgt,c >= 2), a
+ * closed gate leaves zeros in the class's bandwidth, terms, mmd, compactness and shift; compactness_c = the mean of
+ * |x - centroid_tgt,c|^2 over the class's target rows; shift_c = |centroid_src,c - centroid_tgt,c| (not in the
+ * reference).  Global: S = every participating row with unit weights (the USE_CLASS_AWARE_MMD = False branch), gate
+ * n_src >= 2 and n_tgt >= 2.  repulsion = -(mean pairwise distance of the target centroids of the classes with at
+ * least one target row), 0 with fewer than two such classes.  attention_c = exp(lambda (mean(cw) - cw_c)).
+ * ecda_loss = sum over open gates of attention_c (mmd_c + gamma compactness_c + delta repulsion): ECDALoss.forward.
+ *
+ * The distances are those of dad_cluster_metrics, squared (a Gram pass on the fp32 matrix cores on rows centred on
+ * the participating rows' mean; duplicate rows are exactly 0 apart); the exponentials are v_exp_f32 on fp32
+ * coefficients -log2(e) / (bw 2^b + 1e-8); row sums are fp32, everything across rows is double; centroids,
+ * compactness, shift and repulsion are double arithmetic on the fp32 inputs.  Every sum has a fixed order (no
+ * floating-point atomics): two calls on the same inputs write bit-identical outputs.  The calls only enqueue on
+ * `stream` (no host synchronisation; graph-capturable).  out: DAD_DG_SLOTS doubles (device). */
+#define DAD_DG_VALID 0            /* 1.0 when any gate, a class's or the global one, is open */
+#define DAD_DG_N_SRC 1            /* participating source rows */
+#define DAD_DG_N_TGT 2
+#define DAD_DG_NONFINITE 3        /* participating rows with a non-finite component (the block is then meaningless) */
+#define DAD_DG_REPULSION 4
+#define DAD_DG_ECDA_LOSS 5
+#define DAD_DG_MMD_CLASS_MEAN 6   /* mean mmd_c over the open gates (0 without one) */
+#define DAD_DG_G_GATE 8           /* the global set */
+#define DAD_DG_G_BANDWIDTH 9
+#define DAD_DG_G_SS 10
+#define DAD_DG_G_TT 11
+#define DAD_DG_G_ST 12
+#define DAD_DG_G_MMD 13
+#define DAD_DG_C_GATE 16          /* [4] each from here on */
+#define DAD_DG_C_BANDWIDTH 20
+#define DAD_DG_C_SS 24
+#define DAD_DG_C_TT 28
+#define DAD_DG_C_ST 32
+#define DAD_DG_C_MMD 36
+#define DAD_DG_C_N_SRC 40
+#define DAD_DG_C_N_TGT 44
+#define DAD_DG_C_W_TGT 48         /* sum of the class's target weights */
+#define DAD_DG_C_COMPACTNESS 52
+#define DAD_DG_C_SHIFT 56
+#define DAD_DG_C_ATTENTION 60
+#define DAD_DG_SLOTS 64
+#define DAD_DG_MAX_N 65536        /* largest n (both domains together) */
+#define DAD_DG_TILE 64            /* rows / columns of a tile of the pairwise passes */
+#define DAD_DG_MAX_CHUNKS 16      /* most column chunks a row tile is split into */
+typedef struct dad_domain_gap_args {
+  float class_weights[4];         /* cw (DACP's class weights; ones for the plain gap) */
+  double lambda;                  /* ECDA_CLASS_ATTENTION_LAMBDA */
+  double gamma;                   /* ECDA_COMPACTNESS_WEIGHT_GAMMA */
+  double delta;                   /* ECDA_REPULSION_WEIGHT_DELTA */
+} dad_domain_gap_args;
+/* workspace bytes of dad_domain_gap (0 for an unsupported n); no initialisation needed */
+size_t dad_domain_gap_workspace_bytes(int64_t n);
+/* The grid of the two pairwise passes for n rows on a device of `cus` compute units, as dad_cluster_plan.  Host only. */
+int dad_domain_gap_plan(int64_t n, int cus, int* row_tiles, int* chunks, int* tiles_per_chunk);
+/* DAD_E_ARG: emb, labels, domain, args, out or workspace is NULL; DAD_E_SHAPE: n < 1 or n > DAD_DG_MAX_N. */
+int dad_domain_gap(const float* emb, const int64_t* labels, const uint8_t* domain, const float* weights, int64_t n,
+                   const dad_domain_gap_args* args, double* out, void* workspace, void* stream);
+/* dad_domain_gap with the chunk count asked for (clamped as dad_domain_gap_plan clamps it; <= 0: the plan's), for
+ * tests of the chunked summation at small n. */
+int dad_domain_gap_chunked(const float* emb, const int64_t* labels, const uint8_t* domain, const float* weights,
+                           int64_t n, const dad_domain_gap_args* args, double* out, int chunks, void* workspace,
+                           void* stream);
+
 /* --- the reference's helper types as operators (I/utils.py:317-652) -------------------
  * For trainer code that drives DataAugmentation / DACPManager / ECDALoss itself (the
  * train_step shim's callers, anchor calibration, I/train.py:334,341).  Same device functions

@@ -20,11 +20,13 @@ from .trace import TrainingTrace
 from . import checkpoint, evaluate, pretrain
 from .evaluate import cluster_metrics, cluster_metrics_store, separation_report
 from .evaluate import tsne, tsne_affinities, tsne_gradient, tsne_report, tsne_store
+from .evaluate import alignment_report, domain_gap, domain_gap_store, enqueue_domain_gap_store
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
            "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "TrainingTrace",
            "cluster_metrics", "cluster_metrics_store", "separation_report",
-           "tsne", "tsne_affinities", "tsne_gradient", "tsne_store", "tsne_report", "build", "lib"]
+           "tsne", "tsne_affinities", "tsne_gradient", "tsne_store", "tsne_report",
+           "domain_gap", "domain_gap_store", "enqueue_domain_gap_store", "alignment_report", "build", "lib"]
 
 
 def build(verbose=True):

@@ -40,6 +40,13 @@ CM_SLOTS, CM_MAX_N, CM_TILE, CM_MAX_CHUNKS = 16, 65536, 64, 16
 TS_Z, TS_KL, TS_GRAD_NORM, TS_N_ITER, TS_N_CHECKS, TS_SLOTS = 0, 1, 2, 3, 4, 8
 TS_MAX_N, TS_TILE, TS_MAX_CHUNKS, TS_WS_NONFINITE = 16384, 64, 32, 0
 
+# result block of dad_domain_gap (dad.h DAD_DG_*): float64 slots ([4] per class from DG_C_GATE on), limits
+DG_VALID, DG_N_SRC, DG_N_TGT, DG_NONFINITE, DG_REPULSION, DG_ECDA_LOSS, DG_MMD_CLASS_MEAN = range(7)
+DG_G_GATE, DG_G_BANDWIDTH, DG_G_SS, DG_G_TT, DG_G_ST, DG_G_MMD = range(8, 14)
+(DG_C_GATE, DG_C_BANDWIDTH, DG_C_SS, DG_C_TT, DG_C_ST, DG_C_MMD, DG_C_N_SRC, DG_C_N_TGT, DG_C_W_TGT,
+ DG_C_COMPACTNESS, DG_C_SHIFT, DG_C_ATTENTION) = range(16, 64, 4)
+DG_SLOTS, DG_MAX_N, DG_TILE, DG_MAX_CHUNKS = 64, 65536, 64, 16
+
 
 def ts_ld(n):
     """dad.h DAD_TS_LD: the row stride of P."""
@@ -121,6 +128,11 @@ class DadTsneArgs(ctypes.Structure):
     _fields_ = [("max_iter", ctypes.c_int32), ("n_iter_without_progress", ctypes.c_int32),
                 ("early_exaggeration", ctypes.c_double), ("learning_rate", ctypes.c_double),
                 ("min_grad_norm", ctypes.c_double)]
+
+
+class DadDomainGapArgs(ctypes.Structure):
+    _fields_ = [("class_weights", ctypes.c_float * 4), ("lam", ctypes.c_double), ("gamma", ctypes.c_double),
+                ("delta", ctypes.c_double)]      # dad.h dad_domain_gap_args (lam: its `lambda`)
 
 
 # exported symbols (must match include/dad.h); tests check every one is present
@@ -226,6 +238,15 @@ EXPORTS = {
                                                  ctypes.c_void_p]),
     "dad_tsne_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(DadTsneArgs),
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_domain_gap_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "dad_domain_gap_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "dad_domain_gap": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_int64, ctypes.POINTER(DadDomainGapArgs), ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_domain_gap_chunked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_int64, ctypes.POINTER(DadDomainGapArgs), ctypes.c_void_p,
+                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "dad_timing_start": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "dad_timing_kernels": (ctypes.c_int, [ctypes.c_uint]),
     "dad_timing_reset": (ctypes.c_int, []),
@@ -244,7 +265,9 @@ EXPORTS = {
 OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_step_plan_kernels", "dad_trace_bytes", "dad_trace_append",
                     "dad_cluster_workspace_bytes", "dad_cluster_metrics", "dad_cluster_plan",
                     "dad_cluster_metrics_chunked", "dad_tsne_workspace_bytes", "dad_tsne_affinities",
-                    "dad_tsne_gradient", "dad_tsne_plan", "dad_tsne_gradient_chunked", "dad_tsne_run")
+                    "dad_tsne_gradient", "dad_tsne_plan", "dad_tsne_gradient_chunked", "dad_tsne_run",
+                    "dad_domain_gap_workspace_bytes", "dad_domain_gap_plan", "dad_domain_gap",
+                    "dad_domain_gap_chunked")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

@@ -25,6 +25,11 @@ and the 2-D picture those scores describe (dad_tsne_*, csrc/tsne.hip):
 
   tsne_affinities, tsne_gradient, tsne, tsne_store, tsne_report
                       run_tsne: scikit-learn's TSNE(method='exact') (I/iemocap_plot_tsne.py:310-323, 524-525)
+
+and the clean-noisy domain gap of two splits, the quantity the ECDA loss shrinks (dad_domain_gap, csrc/domain_gap.hip):
+
+  domain_gap, domain_gap_store, enqueue_domain_gap_store, alignment_report
+                      ECDALoss._gaussian_kernel / forward on whole splits (I/utils.py:510-652)
 """
 import warnings
 
@@ -690,3 +695,229 @@ def tsne_report(initial_model, trained_model, store_or_loader, **tsne_args):
     return {"initial": a["embedding"].cpu().numpy(), "trained": b["embedding"].cpu().numpy(), "labels": labels,
             "class_counts": [int((labels == c).sum()) for c in range(4)],
             "kl_divergence": (a["kl_divergence"], b["kl_divergence"]), "n_iter": (a["n_iter"], b["n_iter"])}
+
+
+# ------------------------------------------------------------------ the clean-noisy domain gap of two splits
+# ECDALoss (I/utils.py:510-652) is the quantity the method shrinks, computed by the train step on one batch of 64;
+# _gaussian_kernel's [m, m, 256] temporaries rule out a whole split.  dad_domain_gap (csrc/domain_gap.hip) computes
+# it for the embeddings of two splits on the device; one copy of 64 doubles returns every term.
+
+_DG_GLOBAL = (("gate", _lib.DG_G_GATE), ("bandwidth", _lib.DG_G_BANDWIDTH), ("term_ss", _lib.DG_G_SS),
+              ("term_tt", _lib.DG_G_TT), ("term_st", _lib.DG_G_ST), ("mmd", _lib.DG_G_MMD))
+_DG_CLASS = (("gate", _lib.DG_C_GATE), ("bandwidth", _lib.DG_C_BANDWIDTH), ("term_ss", _lib.DG_C_SS),
+             ("term_tt", _lib.DG_C_TT), ("term_st", _lib.DG_C_ST), ("mmd", _lib.DG_C_MMD),
+             ("n_clean", _lib.DG_C_N_SRC), ("n_noisy", _lib.DG_C_N_TGT), ("weight_noisy", _lib.DG_C_W_TGT),
+             ("compactness", _lib.DG_C_COMPACTNESS), ("centroid_shift", _lib.DG_C_SHIFT),
+             ("attention", _lib.DG_C_ATTENTION))
+_DG_COUNTS = ("gate", "n_clean", "n_noisy")
+
+
+def _domain_gap_workspace(n, device):
+    need = int(_lib.require("dad_domain_gap_workspace_bytes", "domain_gap")(int(n)))
+    if need == 0:           # (the library's answer for n outside [1, DG_MAX_N])
+        raise ValueError("the domain gap takes 1 <= rows of both domains together <= %d, got %d" % (_lib.DG_MAX_N, n))
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _domain_gap_args(class_weights, cfg):
+    """dad_domain_gap_args from class_weights [4] (None: ones) and a ConfigView (None: the IEMOCAP defaults)."""
+    from .config import ConfigView
+    view = ConfigView(flavor="iemocap") if cfg is None else cfg
+    a = _lib.DadDomainGapArgs()
+    cw = [1.0] * 4 if class_weights is None else [float(v) for v in torch.as_tensor(class_weights).reshape(-1).tolist()]
+    if len(cw) != 4:
+        raise ValueError("class_weights must be [4]")
+    a.class_weights[:] = cw
+    a.lam = float(view.ECDA_CLASS_ATTENTION_LAMBDA)
+    a.gamma = float(view.ECDA_COMPACTNESS_WEIGHT_GAMMA)
+    a.delta = float(view.ECDA_REPULSION_WEIGHT_DELTA)
+    return a
+
+
+def _enqueue_domain_gap(emb, labels, domain, weights, args, block, ws, chunks=0):
+    """dad_domain_gap on the current stream, enqueue only.  chunks > 0 asks for that many column chunks per row
+    tile instead of the planner's (dad_domain_gap_chunked)."""
+    n = emb.shape[0]
+    stream = torch.cuda.current_stream(emb.device).cuda_stream
+    if chunks:
+        fn = _lib.require("dad_domain_gap_chunked", "domain_gap")
+        rc = fn(_lib.ptr(emb), _lib.ptr(labels), _lib.ptr(domain), _lib.ptr(weights), n, args, _lib.ptr(block),
+                int(chunks), _lib.ptr(ws), stream)
+    else:
+        fn = _lib.require("dad_domain_gap", "domain_gap")
+        rc = fn(_lib.ptr(emb), _lib.ptr(labels), _lib.ptr(domain), _lib.ptr(weights), n, args, _lib.ptr(block),
+                _lib.ptr(ws), stream)
+    _lib.check(rc, "dad_domain_gap")
+
+
+def _domain_gap_result(block):
+    """The dict of domain_gap from the host copy of the DAD_DG_* block."""
+    nbad = int(block[_lib.DG_NONFINITE])
+    n_clean, n_noisy = int(block[_lib.DG_N_SRC]), int(block[_lib.DG_N_TGT])
+    if nbad > 0:
+        raise _lib.DadError("dad_domain_gap: %d of %d participating row(s) have a non-finite embedding component"
+                            % (nbad, n_clean + n_noisy))
+    num = lambda k, v: (bool(v) if k == "gate" else int(v)) if k in _DG_COUNTS else float(v)
+    res = {
+        "valid": bool(block[_lib.DG_VALID]), "n_clean": n_clean, "n_noisy": n_noisy,
+        "global": {k: num(k, block[s]) for k, s in _DG_GLOBAL},
+        "per_class": {k: [num(k, v) for v in block[s:s + 4]] for k, s in _DG_CLASS},
+        "repulsion": float(block[_lib.DG_REPULSION]), "ecda_loss": float(block[_lib.DG_ECDA_LOSS]),
+        "mmd_class_mean": float(block[_lib.DG_MMD_CLASS_MEAN]), "nonfinite": nbad, "block": block,
+    }
+    if not res["valid"]:
+        warnings.warn("the domain gap needs 2 clean and 2 noisy rows, in one class or overall; got %d clean and %d "
+                      "noisy participating rows and no class with 2 of each: every term is 0.0" % (n_clean, n_noisy),
+                      RuntimeWarning, stacklevel=3)
+    return res
+
+
+def domain_gap(emb_clean, labels_clean, emb_noisy, labels_noisy, weights_noisy=None, class_weights=None, cfg=None,
+               _chunks=0):
+    """ECDALoss (I/utils.py:510-652) over two whole sets of embeddings on the device: emb_clean [n_c, 256] and
+    emb_noisy [n_n, 256] (float32, device) under labels_clean / labels_noisy (int64; a row with a label outside
+    [0, 4) takes no part, which is how to apply a DACP mask), weights_noisy [n_n] the noisy rows' sample weights
+    (None: ones; the clean rows' are ones, as in the reference), class_weights [4] DACP's class weights (None:
+    ones), cfg a ConfigView for ECDA_CLASS_ATTENTION_LAMBDA / ECDA_COMPACTNESS_WEIGHT_GAMMA /
+    ECDA_REPULSION_WEIGHT_DELTA (None: the IEMOCAP values).
+    Returns {'valid' (any gate open), 'n_clean', 'n_noisy' (participating rows), 'global': {'gate', 'bandwidth',
+    'term_ss', 'term_tt', 'term_st', 'mmd'} (every participating row, unit weights), 'per_class': the same keys plus
+    'n_clean', 'n_noisy', 'weight_noisy', 'compactness', 'centroid_shift', 'attention', each a list of 4,
+    'repulsion', 'ecda_loss' (ECDALoss.forward), 'mmd_class_mean' (over the open gates), 'nonfinite', 'block'}.
+    A class's gate is open with at least 2 clean and 2 noisy rows; a closed gate's terms are 0.0.  With no gate open
+    'valid' is False and a RuntimeWarning is issued.  Raises DadError when a participating row has a non-finite
+    component, ValueError for mismatched lengths or more than 65,536 rows, before any launch."""
+    emb_clean, emb_noisy = _check_emb(emb_clean), _check_emb(emb_noisy)
+    dev = emb_clean.device
+    if emb_noisy.device != dev:
+        raise ValueError("emb_clean on %s, emb_noisy on %s" % (dev, emb_noisy.device))
+    nc, nn = emb_clean.shape[0], emb_noisy.shape[0]
+    lc = torch.as_tensor(labels_clean).to(device=dev, dtype=torch.int64)
+    ln = torch.as_tensor(labels_noisy).to(device=dev, dtype=torch.int64)
+    if lc.shape != (nc,) or ln.shape != (nn,):
+        raise ValueError("labels_clean must be [%d] and labels_noisy [%d]" % (nc, nn))
+    weights = None
+    if weights_noisy is not None:
+        wn = torch.as_tensor(weights_noisy).to(device=dev, dtype=torch.float32)
+        if wn.shape != (nn,):
+            raise ValueError("weights_noisy must be [%d]" % nn)
+    n = nc + nn
+    if n < 1 or n > _lib.DG_MAX_N:
+        raise ValueError("the domain gap takes 1 <= rows of both domains together <= %d, got %d" % (_lib.DG_MAX_N, n))
+    args = _domain_gap_args(class_weights, cfg)
+    ws = _domain_gap_workspace(n, dev)
+    emb = torch.cat([emb_clean, emb_noisy])
+    labels = torch.cat([lc, ln])
+    domain = torch.zeros(n, dtype=torch.uint8, device=dev)
+    domain[nc:] = 1
+    if weights_noisy is not None:
+        weights = torch.cat([torch.ones(nc, dtype=torch.float32, device=dev), wn])
+    block = torch.empty(_lib.DG_SLOTS, dtype=torch.float64, device=dev)
+    _enqueue_domain_gap(emb, labels, domain, weights, args, block, ws, _chunks)
+    return _domain_gap_result(block.cpu().numpy())
+
+
+def _domain_gap_buffers(plan, n_clean):
+    """The buffers of domain_gap_store on the noisy split's plan for a clean split of n_clean rows, allocated at
+    the first call and reused: workspace, the concatenated embeddings / labels / domain / weights, the teacher's
+    scores, the result block on the device and its pinned host copy."""
+    cache = plan.__dict__.setdefault("_dg", {})
+    b = cache.get(n_clean)
+    if b is None:
+        n, dev = n_clean + plan.n, plan.device
+        if n > _lib.DG_MAX_N:
+            raise ValueError("the domain gap takes 1 <= rows of both domains together <= %d, got %d"
+                             % (_lib.DG_MAX_N, n))
+        b = {"ws": _domain_gap_workspace(n, dev),
+             "emb": torch.empty(n, 256, dtype=torch.float32, device=dev),
+             "labels": torch.empty(n, dtype=torch.int64, device=dev),
+             "domain": torch.cat([torch.zeros(n_clean, dtype=torch.uint8, device=dev),
+                                  torch.ones(plan.n, dtype=torch.uint8, device=dev)]),
+             "weights": torch.ones(n, dtype=torch.float32, device=dev),
+             "score": torch.empty(plan.n, dtype=torch.float32, device=dev),
+             "block_d": torch.zeros(_lib.DG_SLOTS, dtype=torch.float64, device=dev),
+             "block_h": torch.zeros(_lib.DG_SLOTS, dtype=torch.float64).pin_memory()}
+        cache[n_clean] = b
+    return b
+
+
+def enqueue_domain_gap_store(model, clean_plan, noisy_plan, assign="labels", thresholds=None, class_weights=None,
+                             precision="fp32", cfg=None):
+    """The enqueue part of domain_gap_store (no copy to the host, no synchronisation; graph-capturable): one
+    dad_eval_split per split for the student embeddings (the noisy one with the teacher for assign='teacher'),
+    dad_certainty_scores for the teacher's scores, dad_domain_gap behind them on the current stream.  Returns the
+    buffers (_domain_gap_buffers): the block lands in ['block_d']."""
+    if assign not in ("labels", "teacher"):
+        raise ValueError("assign must be 'labels' or 'teacher', got %r" % (assign,))
+    if clean_plan.labels_d is None or (assign == "labels" and noisy_plan.labels_d is None):
+        raise ValueError("the split has no labels")
+    if clean_plan.device != noisy_plan.device:
+        raise ValueError("clean split on %s, noisy split on %s" % (clean_plan.device, noisy_plan.device))
+    nc = clean_plan.n
+    b = _domain_gap_buffers(noisy_plan, nc)
+    args = _domain_gap_args(class_weights, cfg)
+    b["emb"][:nc].copy_(_enqueue_embeddings(model, clean_plan, False, precision))
+    b["labels"][:nc].copy_(clean_plan.labels_d)
+    if assign == "labels":
+        b["emb"][nc:].copy_(_enqueue_embeddings(model, noisy_plan, False, precision))
+        b["labels"][nc:].copy_(noisy_plan.labels_d)
+        b["weights"][nc:].fill_(1.0)
+    else:
+        from .config import ConfigView
+        view = ConfigView(flavor="iemocap") if cfg is None else cfg
+        out = enqueue_eval_split(model, noisy_plan, use_teacher=True, precision=precision,
+                                 outputs=("emb", "t_pred", "t_logits"))
+        b["emb"][nc:].copy_(out["emb"])
+        probs = torch.softmax(out["t_logits"], dim=1).contiguous()
+        stream = torch.cuda.current_stream(noisy_plan.device).cuda_stream
+        _lib.check(_lib.lib().dad_certainty_scores(probs.data_ptr(), noisy_plan.n,
+                                                   int(view.effective_switches()[2]), b["score"].data_ptr(),
+                                                   None, stream), "dad_certainty_scores")
+        b["weights"][nc:].copy_(b["score"])
+        pred = out["t_pred"]
+        if thresholds is not None:
+            thr = torch.as_tensor(thresholds).to(device=noisy_plan.device, dtype=torch.float32)
+            if thr.shape != (4,):
+                raise ValueError("thresholds must be [4]")
+            # calculate_mask (I/utils.py:449-507): confident where score > thresholds[pred]; the rest take no part
+            pred = torch.where(b["score"] > thr[pred], pred, torch.full_like(pred, -1))
+        b["labels"][nc:].copy_(pred)
+    _enqueue_domain_gap(b["emb"], b["labels"], b["domain"], b["weights"], args, b["block_d"], b["ws"])
+    return b
+
+
+def domain_gap_store(model, clean_split, noisy_split, assign="labels", thresholds=None, class_weights=None,
+                     precision="fp32", cfg=None):
+    """domain_gap of the student's eval-mode embeddings of two FeatureStore splits without their leaving the
+    device: one dad_eval_split per split, one dad_domain_gap, one copy of the block.  assign='labels': the noisy
+    rows under their true labels with unit weights (the plain domain gap).  assign='teacher': what the loss would
+    see split-wide -- each noisy row under the teacher's prediction, weighted by the teacher's certainty score
+    (dad_certainty_scores of its softmax); with thresholds [4], rows with score <= thresholds[prediction] take no
+    part (calculate_mask's comparison, I/utils.py:449-507).  Every buffer is cached on the noisy split's EvalPlan."""
+    model.eval()
+    cp, np_ = EvalPlan.of(clean_split), EvalPlan.of(noisy_split)
+    b = enqueue_domain_gap_store(model, cp, np_, assign, thresholds, class_weights, precision, cfg)
+    b["block_h"].copy_(b["block_d"], non_blocking=True)
+    torch.cuda.current_stream(np_.device).synchronize()
+    return _domain_gap_result(b["block_h"].numpy().copy())
+
+
+def alignment_from_gaps(initial, trained):
+    """The `initial_weights` / `trained_weights` / `improvement` block (the shape of separation_from_metrics) from
+    two domain_gap dicts: the global mmd, the mean per-class mmd and the ECDA loss; a gap that shrank has a
+    negative change.  Every value a Python float."""
+    pick = lambda r: {"mmd_global": float(r["global"]["mmd"]), "mmd_class_mean": float(r["mmd_class_mean"]),
+                      "ecda_loss": float(r["ecda_loss"])}
+    a, b = pick(initial), pick(trained)
+    return {"initial_weights": a, "trained_weights": b,
+            "improvement": {"mmd_global_change": b["mmd_global"] - a["mmd_global"],
+                            "mmd_class_mean_change": b["mmd_class_mean"] - a["mmd_class_mean"],
+                            "ecda_loss_change": b["ecda_loss"] - a["ecda_loss"],
+                            "mmd_global_percentage": ((b["mmd_global"] - a["mmd_global"]) / abs(a["mmd_global"]) * 100
+                                                      if a["mmd_global"] != 0 else 0.0)}}
+
+
+def alignment_report(initial_model, trained_model, clean_split, noisy_split, **gap_args):
+    """alignment_from_gaps of domain_gap_store under the initial and the trained weights."""
+    return alignment_from_gaps(domain_gap_store(initial_model, clean_split, noisy_split, **gap_args),
+                               domain_gap_store(trained_model, clean_split, noisy_split, **gap_args))
