@@ -697,6 +697,79 @@ int dad_domain_gap_chunked(const float* emb, const int64_t* labels, const uint8_
                            int64_t n, const dad_domain_gap_args* args, double* out, int chunks, void* workspace,
                            void* stream);
 
+/* --- exact k nearest neighbours of a split's embeddings and their scores (csrc/knn.hip) ----
+ * Not in the reference; the yardstick is scikit-learn 1.7.2 (NearestNeighbors(algorithm='brute'),
+ * KNeighborsClassifier(weights='uniform'), sklearn.manifold.trustworthiness).  Every call only enqueues on `stream`
+ * (no host synchronisation; graph-capturable) and uses no floating-point atomics.  One workspace of
+ * dad_knn_workspace_bytes(n, k) serves dad_knn and dad_trustworthiness; it needs no initialisation.
+ *
+ * dad_knn: the k nearest candidates of every row of emb [n][256] (dad_eval_split's emb / t_emb).  group [n] (NULL:
+ * every row in group 0): a row with group < 0 is neither a query nor a candidate, and is left out by selection (its
+ * values, NaN included, reach no other row's result).  The candidates of row i are the participating rows j != i
+ * with, by mode, DAD_KNN_ALL: every one; DAD_KNN_SAME: group[j] == group[i]; DAD_KNN_OTHER: group[j] != group[i]
+ * (group = the domain: one call answers noisy -> clean and clean -> noisy).  The distance is D_ij = max(|a_i|^2 +
+ * |a_j|^2 - 2 a_i.a_j, 0) on the fp32 matrix cores, a = the rows minus the fp32 mean of the participating rows, |a_i|^2
+ * the diagonal of the same Gram block -- with group NULL the bits dad_tsne_affinities sees, and dad_cluster_metrics'
+ * distances squared.  The order is ascending in the pair (D_ij, j): ties go to the smaller index, a stable argsort.
+ * idx [n][k] int32 and d2 [n][k] floats (device) receive the neighbours and their D; entries a row has no candidate
+ * for (fewer than k candidates, or a row that takes no part) are -1 and +inf.  The selection is a total order on
+ * bits that do not depend on the chunking: every chunk count, and every call, writes the same bits.  Rows past n are
+ * never read.  The participating rows with a non-finite component are counted into the int32 at word
+ * DAD_KNN_WS_NONFINITE of the workspace (idx and d2 are then meaningless).
+ * DAD_E_ARG: emb, idx, d2 or workspace is NULL, or an unknown mode; DAD_E_SHAPE: k outside [1, DAD_KNN_MAX_K] or n
+ * outside [1, DAD_KNN_MAX_N]. */
+#define DAD_KNN_ALL 0
+#define DAD_KNN_SAME 1
+#define DAD_KNN_OTHER 2
+#define DAD_KNN_MAX_K 32
+#define DAD_KNN_MAX_N 65536
+#define DAD_KNN_TILE 64           /* rows / columns of a tile of the pairwise pass */
+#define DAD_KNN_MAX_CHUNKS 16     /* most column chunks a row tile is split into */
+#define DAD_KNN_WS_NONFINITE 0    /* int32 word of the workspace: participating rows with a non-finite component */
+/* workspace bytes of dad_knn / dad_trustworthiness (0 for an unsupported n or k) */
+size_t dad_knn_workspace_bytes(int64_t n, int k);
+int dad_knn(const float* emb, const int32_t* group, int64_t n, int k, int mode, int32_t* idx, float* d2,
+            void* workspace, void* stream);
+/* The grid of the pairwise pass for n rows and k neighbours on a device of `cus` compute units, as
+ * dad_cluster_plan (up to k = 16 two workgroups share a compute unit, above it one: the lists live in LDS).
+ * Host only. */
+int dad_knn_plan(int64_t n, int k, int cus, int* row_tiles, int* chunks, int* tiles_per_chunk);
+/* dad_knn with the chunk count asked for (clamped as dad_knn_plan clamps it; <= 0: the plan's), for tests. */
+int dad_knn_chunked(const float* emb, const int32_t* group, int64_t n, int k, int mode, int32_t* idx, float* d2,
+                    int chunks, void* workspace, void* stream);
+/* dad_knn_vote: the uniform vote over idx [n][k] (dad_knn's).  Each neighbour j >= 0 with labels[j] in [0, 4) casts
+ * one vote; the first maximum wins (the smallest class on a tie, scikit-learn's rule).  pred [n] int64: the winner,
+ * -1 for a row without a voting neighbour or with group < 0 (group NULL: every row in group 0).  out
+ * [DAD_KV_SLOTS] int64 (device; the call clears it): over the query rows -- group >= 0 and an own label in [0, 4) --
+ * confusion[g][label][pred] with g = (group != 0), the query count per g, and per g the queries without a vote (in
+ * no confusion cell).  DAD_E_ARG: idx, labels, pred or out is NULL; DAD_E_SHAPE: as dad_knn. */
+#define DAD_KV_CONFUSION 0        /* [2][4][4] */
+#define DAD_KV_QUERIES 32         /* [2] */
+#define DAD_KV_NO_VOTE 34         /* [2] */
+#define DAD_KV_SLOTS 40
+int dad_knn_vote(const int32_t* idx, const int64_t* labels, const int32_t* group, int64_t n, int k, int64_t* pred,
+                 int64_t* out, void* stream);
+/* dad_trustworthiness: sklearn.manifold.trustworthiness(emb, Y, n_neighbors = k) for Y [n][2] floats.  The k nearest
+ * rows of each row in Y by (|y_i - y_j|^2, j), the distance (dx * dx) + (dy * dy) of the fp32 differences, each
+ * operation rounded; for each such neighbour j the rank r(i, j) = 1 + #{l not in {i, j} : (D_il, l) < (D_ij, j)}
+ * with dad_knn's D over all rows (scikit-learn leaves the order of equal distances to its sort; here it is the
+ * index); penalty_i = sum_j max(0, r(i, j) - k); T = 1 - 2 sum_i penalty_i / (n k (2 n - 3 k - 1)) in double.  The
+ * counts are int32 and exact, so the result does not depend on the chunking.  out [DAD_TW_SLOTS] doubles (device);
+ * penalty [n] int32 (device, may be NULL) receives penalty_i.  DAD_E_ARG: emb, Y, out or workspace is NULL;
+ * DAD_E_SHAPE: unless 1 <= k < n / 2 (scikit-learn's rule), k <= DAD_KNN_MAX_K and n <= DAD_KNN_MAX_N. */
+#define DAD_TW_T 0
+#define DAD_TW_PENALTY 1          /* sum_i penalty_i (exact below 2^53) */
+#define DAD_TW_N 2
+#define DAD_TW_K 3
+#define DAD_TW_VALID 4            /* 1.0 when no row is non-finite */
+#define DAD_TW_NONFINITE 5        /* rows of emb plus rows of Y with a non-finite component (T is then meaningless) */
+#define DAD_TW_SLOTS 8
+int dad_trustworthiness(const float* emb, const float* Y, int64_t n, int k, double* out, int32_t* penalty,
+                        void* workspace, void* stream);
+/* dad_trustworthiness with the chunk count of the counting pass asked for (<= 0: dad_knn_plan's), for tests. */
+int dad_trustworthiness_chunked(const float* emb, const float* Y, int64_t n, int k, double* out, int32_t* penalty,
+                                int chunks, void* workspace, void* stream);
+
 /* --- the reference's helper types as operators (I/utils.py:317-652) -------------------
  * For trainer code that drives DataAugmentation / DACPManager / ECDALoss itself (the
  * train_step shim's callers, anchor calibration, I/train.py:334,341).  Same device functions

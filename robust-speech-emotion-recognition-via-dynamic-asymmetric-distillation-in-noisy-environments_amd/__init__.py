@@ -21,12 +21,16 @@ from . import checkpoint, evaluate, pretrain
 from .evaluate import cluster_metrics, cluster_metrics_store, separation_report
 from .evaluate import tsne, tsne_affinities, tsne_gradient, tsne_report, tsne_store
 from .evaluate import alignment_report, domain_gap, domain_gap_store, enqueue_domain_gap_store
+from .evaluate import (cross_domain_knn_store, knn, knn_accuracy, knn_store, neighbourhood_report,
+                       trustworthiness)
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
            "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "TrainingTrace",
            "cluster_metrics", "cluster_metrics_store", "separation_report",
            "tsne", "tsne_affinities", "tsne_gradient", "tsne_store", "tsne_report",
-           "domain_gap", "domain_gap_store", "enqueue_domain_gap_store", "alignment_report", "build", "lib"]
+           "domain_gap", "domain_gap_store", "enqueue_domain_gap_store", "alignment_report",
+           "knn", "knn_accuracy", "knn_store", "cross_domain_knn_store", "trustworthiness", "neighbourhood_report",
+           "build", "lib"]
 
 
 def build(verbose=True):

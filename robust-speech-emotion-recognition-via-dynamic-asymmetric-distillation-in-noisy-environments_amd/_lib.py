@@ -47,6 +47,13 @@ DG_G_GATE, DG_G_BANDWIDTH, DG_G_SS, DG_G_TT, DG_G_ST, DG_G_MMD = range(8, 14)
  DG_C_COMPACTNESS, DG_C_SHIFT, DG_C_ATTENTION) = range(16, 64, 4)
 DG_SLOTS, DG_MAX_N, DG_TILE, DG_MAX_CHUNKS = 64, 65536, 64, 16
 
+# dad_knn / dad_knn_vote / dad_trustworthiness (dad.h DAD_KNN_*, DAD_KV_*, DAD_TW_*): modes and limits, the workspace
+# word of the non-finite count, the int64 slots of the vote's block, the float64 slots of the trustworthiness block
+KNN_ALL, KNN_SAME, KNN_OTHER = 0, 1, 2
+KNN_MAX_K, KNN_MAX_N, KNN_TILE, KNN_MAX_CHUNKS, KNN_WS_NONFINITE = 32, 65536, 64, 16, 0
+KV_CONFUSION, KV_QUERIES, KV_NO_VOTE, KV_SLOTS = 0, 32, 34, 40
+TW_T, TW_PENALTY, TW_N, TW_K, TW_VALID, TW_NONFINITE, TW_SLOTS = 0, 1, 2, 3, 4, 5, 8
+
 
 def ts_ld(n):
     """dad.h DAD_TS_LD: the row stride of P."""
@@ -247,6 +254,21 @@ EXPORTS = {
     "dad_domain_gap_chunked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_int64, ctypes.POINTER(DadDomainGapArgs), ctypes.c_void_p,
                                               ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_knn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "dad_knn_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                    ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "dad_knn": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_knn_chunked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                       ctypes.c_void_p]),
+    "dad_knn_vote": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_trustworthiness": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_trustworthiness_chunked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                   ctypes.c_void_p]),
     "dad_timing_start": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "dad_timing_kernels": (ctypes.c_int, [ctypes.c_uint]),
     "dad_timing_reset": (ctypes.c_int, []),
@@ -267,7 +289,8 @@ OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_step_plan_kernels", "dad_trace_
                     "dad_cluster_metrics_chunked", "dad_tsne_workspace_bytes", "dad_tsne_affinities",
                     "dad_tsne_gradient", "dad_tsne_plan", "dad_tsne_gradient_chunked", "dad_tsne_run",
                     "dad_domain_gap_workspace_bytes", "dad_domain_gap_plan", "dad_domain_gap",
-                    "dad_domain_gap_chunked")
+                    "dad_domain_gap_chunked", "dad_knn_workspace_bytes", "dad_knn_plan", "dad_knn", "dad_knn_chunked",
+                    "dad_knn_vote", "dad_trustworthiness", "dad_trustworthiness_chunked")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

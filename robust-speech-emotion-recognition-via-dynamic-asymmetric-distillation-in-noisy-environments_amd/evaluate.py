@@ -30,6 +30,12 @@ and the clean-noisy domain gap of two splits, the quantity the ECDA loss shrinks
 
   domain_gap, domain_gap_store, enqueue_domain_gap_store, alignment_report
                       ECDALoss._gaussian_kernel / forward on whole splits (I/utils.py:510-652)
+
+and the neighbour structure of a split's embeddings (dad_knn, dad_knn_vote, dad_trustworthiness, csrc/knn.hip):
+
+  knn, knn_accuracy, knn_store, cross_domain_knn_store, trustworthiness, neighbourhood_report
+                      not in the reference: scikit-learn's NearestNeighbors(brute), KNeighborsClassifier's vote and
+                      sklearn.manifold.trustworthiness
 """
 import warnings
 
@@ -673,28 +679,43 @@ def tsne(emb, perplexity=30.0, max_iter=1000, init="pca", learning_rate="auto", 
     return res
 
 
+def _tsne_store(model, plan, use_teacher=False, precision="fp32", **tsne_args):
+    """(the split's eval-mode embeddings on the device, tsne of them): what tsne_store runs."""
+    model.eval()
+    emb = _enqueue_embeddings(model, plan, use_teacher, precision)
+    return emb, tsne(emb, **tsne_args)
+
+
 def tsne_store(model, store_or_loader, use_teacher=False, precision="fp32", **tsne_args):
     """tsne of the split's eval-mode embeddings (the teacher's with use_teacher), which dad_eval_split leaves on the
     device: the embeddings never reach the host."""
-    model.eval()
-    plan = EvalPlan.of(store_or_loader)
-    return tsne(_enqueue_embeddings(model, plan, use_teacher, precision), **tsne_args)
+    return _tsne_store(model, EvalPlan.of(store_or_loader), use_teacher, precision, **tsne_args)[1]
 
 
-def tsne_report(initial_model, trained_model, store_or_loader, **tsne_args):
+def tsne_report(initial_model, trained_model, store_or_loader, trustworthiness_k=None, **tsne_args):
     """The inputs of the reference's plot_tsne_comparison (I/iemocap_plot_tsne.py:524-525 and the plot call) for
     one split: {'initial' [n, 2], 'trained' [n, 2] NumPy float32 embeddings under the two weight sets (student
     embeddings, as iemocap_plot_tsne.py embeds with), 'labels' [n], 'class_counts' [4], 'kl_divergence' (initial,
-    trained), 'n_iter' (initial, trained)}."""
+    trained), 'n_iter' (initial, trained)}.  With trustworthiness_k the report gains 'trustworthiness' (initial,
+    trained): scikit-learn's trustworthiness of each map against the embeddings it was made from, n_neighbors =
+    trustworthiness_k (trustworthiness(); unlike the error, a number two runs can be compared by)."""
     plan = EvalPlan.of(store_or_loader)
     if plan.labels_d is None:
         raise ValueError("the split has no labels")
-    a = tsne_store(initial_model, plan, **tsne_args)
-    b = tsne_store(trained_model, plan, **tsne_args)
+    sides = []
+    for model in (initial_model, trained_model):
+        emb, r = _tsne_store(model, plan, **tsne_args)
+        if trustworthiness_k is not None:
+            r["trustworthiness"] = trustworthiness(emb, r["embedding"], k=trustworthiness_k)["trustworthiness"]
+        sides.append(r)
+    a, b = sides
     labels = plan.labels_d.cpu().numpy()
-    return {"initial": a["embedding"].cpu().numpy(), "trained": b["embedding"].cpu().numpy(), "labels": labels,
-            "class_counts": [int((labels == c).sum()) for c in range(4)],
-            "kl_divergence": (a["kl_divergence"], b["kl_divergence"]), "n_iter": (a["n_iter"], b["n_iter"])}
+    rep = {"initial": a["embedding"].cpu().numpy(), "trained": b["embedding"].cpu().numpy(), "labels": labels,
+           "class_counts": [int((labels == c).sum()) for c in range(4)],
+           "kl_divergence": (a["kl_divergence"], b["kl_divergence"]), "n_iter": (a["n_iter"], b["n_iter"])}
+    if trustworthiness_k is not None:
+        rep["trustworthiness"] = (a["trustworthiness"], b["trustworthiness"])
+    return rep
 
 
 # ------------------------------------------------------------------ the clean-noisy domain gap of two splits
@@ -921,3 +942,267 @@ def alignment_report(initial_model, trained_model, clean_split, noisy_split, **g
     """alignment_from_gaps of domain_gap_store under the initial and the trained weights."""
     return alignment_from_gaps(domain_gap_store(initial_model, clean_split, noisy_split, **gap_args),
                                domain_gap_store(trained_model, clean_split, noisy_split, **gap_args))
+
+
+# ------------------------------------------------------------------ exact k nearest neighbours of a split
+# The neighbour structure of the embeddings (dad_knn, csrc/knn.hip: exact top-k selection inside the Gram walk of the
+# other pairwise evaluators) and the three scores on it: the leave-one-out k-NN vote (a non-parametric reading of class
+# separation beside silhouette and CH), cross-domain retrieval (the per-utterance counterpart of domain_gap) and
+# scikit-learn's trustworthiness of a t-SNE map.  Not in the reference; the yardstick is scikit-learn 1.7.2.
+
+_KNN_MODES = {"all": _lib.KNN_ALL, "same": _lib.KNN_SAME, "other": _lib.KNN_OTHER}
+_KV_RESULT = _lib.KV_SLOTS + 1          # the vote's block, then dad_knn's non-finite count
+
+
+def _knn_workspace(n, k, device):
+    need = int(_lib.require("dad_knn_workspace_bytes", "knn")(int(n), int(k)))
+    if need == 0:           # (the library's answer for n or k outside its limits)
+        raise ValueError("knn takes 1 <= n <= %d rows and 1 <= k <= %d, got n = %d, k = %d"
+                         % (_lib.KNN_MAX_N, _lib.KNN_MAX_K, n, k))
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _enqueue_knn(emb, group, k, mode, idx, d2, ws, chunks=0):
+    """dad_knn on the current stream, enqueue only.  chunks > 0 asks for that many column chunks per row tile
+    instead of the planner's (dad_knn_chunked)."""
+    fn = _lib.require("dad_knn_chunked", "knn")
+    _lib.check(fn(_lib.ptr(emb), _lib.ptr(group), emb.shape[0], int(k), int(mode), _lib.ptr(idx), _lib.ptr(d2),
+                  int(chunks), _lib.ptr(ws), torch.cuda.current_stream(emb.device).cuda_stream), "dad_knn")
+
+
+def _enqueue_knn_vote(idx, labels, group, pred, result, ws):
+    """dad_knn_vote on the current stream, enqueue only; result [_KV_RESULT] int64 receives the vote's block and,
+    behind it, the non-finite count dad_knn left in ws."""
+    fn = _lib.require("dad_knn_vote", "knn")
+    _lib.check(fn(_lib.ptr(idx), _lib.ptr(labels), _lib.ptr(group), idx.shape[0], idx.shape[1], _lib.ptr(pred),
+                  _lib.ptr(result), torch.cuda.current_stream(idx.device).cuda_stream), "dad_knn_vote")
+    w = 4 * _lib.KNN_WS_NONFINITE
+    result[_lib.KV_SLOTS:].copy_(ws[w:w + 4].view(torch.int32))
+
+
+def _knn_group(labels, domain=None):
+    """The int32 group of dad_knn from labels [n] (a label outside [0, 4) takes no part) and an optional domain."""
+    ok = (labels >= 0) & (labels < 4)
+    g = torch.zeros_like(labels, dtype=torch.int32) if domain is None else (domain != 0).to(torch.int32)
+    return torch.where(ok, g, torch.full_like(g, -1)).contiguous()
+
+
+def knn(emb, k=5, group=None, mode="all", _chunks=0):
+    """The k nearest rows of every row of emb [n, 256] (float32, device), exactly: device tensors (idx [n, k] int32,
+    d2 [n, k] float32), ascending in (squared distance, index), the distances those of cluster_metrics, squared.
+    group [n] (int; None: one group): a row with a negative group is neither a query nor a candidate.  mode 'all':
+    every other participating row is a candidate; 'same': those of the row's own group; 'other': those of the other
+    groups (group = the domain: one call answers noisy -> clean and clean -> noisy).  Entries without a candidate
+    are -1 / inf.  Every call and every chunk count gives the same bits.  Raises ValueError for n or k outside
+    [1, 65536] / [1, 32], before any launch, and DadError when a participating row has a non-finite component."""
+    emb = _check_emb(emb)
+    n = emb.shape[0]
+    if mode not in _KNN_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (", ".join(_KNN_MODES), mode))
+    if group is not None:
+        group = torch.as_tensor(group).to(device=emb.device, dtype=torch.int32).contiguous()
+        if group.shape != (n,):
+            raise ValueError("group must be [n]")
+    ws = _knn_workspace(n, k, emb.device)
+    idx = torch.empty(n, int(k), dtype=torch.int32, device=emb.device)
+    d2 = torch.empty(n, int(k), dtype=torch.float32, device=emb.device)
+    _enqueue_knn(emb, group, k, _KNN_MODES[mode], idx, d2, ws, _chunks)
+    w = 4 * _lib.KNN_WS_NONFINITE
+    nbad = int(ws[w:w + 4].view(torch.int32).item())
+    if nbad > 0:
+        raise _lib.DadError("dad_knn: %d participating row(s) of %d have a non-finite embedding component" % (nbad, n))
+    return idx, d2
+
+
+def _knn_result(result, pred, with_domain):
+    """knn_accuracy's dict(s) from the host copy of the result words."""
+    nbad = int(result[_lib.KV_SLOTS])
+    if nbad > 0:
+        raise _lib.DadError("dad_knn: %d participating row(s) have a non-finite embedding component" % nbad)
+    out = []
+    for g in (0, 1):
+        cm = result[_lib.KV_CONFUSION + 16 * g:_lib.KV_CONFUSION + 16 * (g + 1)].reshape(4, 4).copy()
+        nq, nv = int(result[_lib.KV_QUERIES + g]), int(result[_lib.KV_NO_VOTE + g])
+        if cm.sum() == 0:
+            out.append(None)
+            continue
+        r = metrics_from_confusion(cm)
+        r.update({"n_queries": nq, "n_no_vote": nv, "pred": pred, "block": result})
+        out.append(r)
+    if with_domain:
+        return {0: out[0], 1: out[1]}
+    if out[0] is None:
+        raise ValueError("no row has a voting neighbour")
+    return out[0]
+
+
+def knn_accuracy(emb, labels, k=5, domain=None, mode="all"):
+    """The leave-one-out k-NN vote on emb [n, 256] (float32, device) under labels [n]: each row with a label in
+    [0, 4) is classified by the uniform vote of its k nearest candidates (knn; rows with another label take no
+    part), the smallest class winning a tie (KNeighborsClassifier's rule).  Returns metrics_from_confusion of the
+    vote plus 'pred' [n] (int64 device tensor, -1 for a row that takes no part or has no neighbour), 'n_queries'
+    and 'n_no_vote' (queries without a candidate: in no cell of the confusion matrix).  With domain [n] (0 / non-zero)
+    the rows' group is their domain, mode applies to it ('other': retrieval across the domains) and the result is
+    {0: the dict of the queries of domain 0, 1: of the others} (None for a domain without a voting query)."""
+    emb = _check_emb(emb)
+    n = emb.shape[0]
+    if mode not in _KNN_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (", ".join(_KNN_MODES), mode))
+    labels = torch.as_tensor(labels).to(device=emb.device, dtype=torch.int64).contiguous()
+    if labels.shape != (n,):
+        raise ValueError("labels must be [n]")
+    if domain is not None:
+        domain = torch.as_tensor(domain).to(device=emb.device)
+        if domain.shape != (n,):
+            raise ValueError("domain must be [n]")
+    group = _knn_group(labels, domain)
+    ws = _knn_workspace(n, k, emb.device)
+    idx = torch.empty(n, int(k), dtype=torch.int32, device=emb.device)
+    d2 = torch.empty(n, int(k), dtype=torch.float32, device=emb.device)
+    pred = torch.empty(n, dtype=torch.int64, device=emb.device)
+    result = torch.empty(_KV_RESULT, dtype=torch.int64, device=emb.device)
+    _enqueue_knn(emb, group, k, _KNN_MODES[mode], idx, d2, ws)
+    _enqueue_knn_vote(idx, labels, group, pred, result, ws)
+    return _knn_result(result.cpu().numpy(), pred, domain is not None)
+
+
+def _knn_buffers(plan, n, k):
+    """The buffers of knn_store / cross_domain_knn_store on a split's plan for n rows in all, allocated at the first
+    call and reused."""
+    cache = plan.__dict__.setdefault("_knn", {})
+    b = cache.get((n, int(k)))
+    if b is None:
+        dev = plan.device
+        b = {"ws": _knn_workspace(n, k, dev),
+             "idx": torch.empty(n, int(k), dtype=torch.int32, device=dev),
+             "d2": torch.empty(n, int(k), dtype=torch.float32, device=dev),
+             "pred": torch.empty(n, dtype=torch.int64, device=dev),
+             "result_d": torch.zeros(_KV_RESULT, dtype=torch.int64, device=dev),
+             "result_h": torch.zeros(_KV_RESULT, dtype=torch.int64).pin_memory()}
+        cache[(n, int(k))] = b
+    return b
+
+
+def _read_knn(b, device, with_domain):
+    b["result_h"].copy_(b["result_d"], non_blocking=True)
+    torch.cuda.current_stream(device).synchronize()
+    return _knn_result(b["result_h"].numpy().copy(), b["pred"].clone(), with_domain)
+
+
+def enqueue_knn_store(model, plan, k=5, use_teacher=False, precision="fp32"):
+    """The enqueue part of knn_store (no copy to the host, no synchronisation; graph-capturable): dad_eval_split for
+    the embeddings, dad_knn and dad_knn_vote behind it.  Returns the buffers: the result lands in ['result_d']."""
+    if plan.labels_d is None:
+        raise ValueError("the split has no labels")
+    b = _knn_buffers(plan, plan.n, k)
+    emb = _enqueue_embeddings(model, plan, use_teacher, precision)
+    group = _knn_group(plan.labels_d)
+    _enqueue_knn(emb, group, k, _lib.KNN_ALL, b["idx"], b["d2"], b["ws"])
+    _enqueue_knn_vote(b["idx"], plan.labels_d, group, b["pred"], b["result_d"], b["ws"])
+    return b
+
+
+def knn_store(model, store_or_loader, k=5, use_teacher=False, precision="fp32"):
+    """knn_accuracy of the split's eval-mode embeddings (the teacher's with use_teacher) without their leaving the
+    device: one dad_eval_split, one dad_knn, one dad_knn_vote, one copy of the result words."""
+    model.eval()
+    plan = EvalPlan.of(store_or_loader)
+    return _read_knn(enqueue_knn_store(model, plan, k, use_teacher, precision), plan.device, False)
+
+
+def enqueue_cross_domain_knn_store(model, clean_plan, noisy_plan, k=5, precision="fp32"):
+    """The enqueue part of cross_domain_knn_store (no copy to the host, no synchronisation): one dad_eval_split per
+    split into one concatenated buffer (the clean rows first), dad_knn with the domain as the group and mode
+    'other', dad_knn_vote.  Returns the buffers: the result lands in ['result_d']."""
+    if clean_plan.labels_d is None or noisy_plan.labels_d is None:
+        raise ValueError("the split has no labels")
+    if clean_plan.device != noisy_plan.device:
+        raise ValueError("clean split on %s, noisy split on %s" % (clean_plan.device, noisy_plan.device))
+    nc, n = clean_plan.n, clean_plan.n + noisy_plan.n
+    if n > _lib.KNN_MAX_N:
+        raise ValueError("knn takes at most %d rows of both domains together, got %d" % (_lib.KNN_MAX_N, n))
+    b = _knn_buffers(noisy_plan, n, k)
+    if "emb" not in b:
+        dev = noisy_plan.device
+        b["emb"] = torch.empty(n, 256, dtype=torch.float32, device=dev)
+        b["labels"] = torch.empty(n, dtype=torch.int64, device=dev)
+        b["domain"] = torch.cat([torch.zeros(nc, dtype=torch.int32, device=dev),
+                                 torch.ones(noisy_plan.n, dtype=torch.int32, device=dev)])
+    b["emb"][:nc].copy_(_enqueue_embeddings(model, clean_plan, False, precision))
+    b["emb"][nc:].copy_(_enqueue_embeddings(model, noisy_plan, False, precision))
+    b["labels"][:nc].copy_(clean_plan.labels_d)
+    b["labels"][nc:].copy_(noisy_plan.labels_d)
+    group = _knn_group(b["labels"], b["domain"])
+    _enqueue_knn(b["emb"], group, k, _lib.KNN_OTHER, b["idx"], b["d2"], b["ws"])
+    _enqueue_knn_vote(b["idx"], b["labels"], group, b["pred"], b["result_d"], b["ws"])
+    return b
+
+
+def cross_domain_knn_store(model, clean_split, noisy_split, k=5, precision="fp32"):
+    """Retrieval across the domains with the student's eval-mode embeddings of two FeatureStore splits: every noisy
+    utterance is classified by its k nearest clean ones and every clean utterance by its k nearest noisy ones, in one
+    dad_knn over both.  Returns {'noisy_to_clean': knn_accuracy's dict over the noisy queries, 'clean_to_noisy': over
+    the clean ones}; 'pred' covers the concatenated rows, the clean split's first."""
+    model.eval()
+    cp, np_ = EvalPlan.of(clean_split), EvalPlan.of(noisy_split)
+    r = _read_knn(enqueue_cross_domain_knn_store(model, cp, np_, k, precision), np_.device, True)
+    return {"noisy_to_clean": r[1], "clean_to_noisy": r[0]}
+
+
+def _enqueue_trustworthiness(emb, Y, k, out, penalty, ws, chunks=0):
+    fn = _lib.require("dad_trustworthiness_chunked", "trustworthiness")
+    _lib.check(fn(_lib.ptr(emb), _lib.ptr(Y), emb.shape[0], int(k), _lib.ptr(out), _lib.ptr(penalty), int(chunks),
+                  _lib.ptr(ws), torch.cuda.current_stream(emb.device).cuda_stream), "dad_trustworthiness")
+
+
+def trustworthiness(emb, Y, k=5, samples=False, _chunks=0):
+    """sklearn.manifold.trustworthiness(emb, Y, n_neighbors=k) on the device, for emb [n, 256] and its map Y [n, 2]
+    (float32, device): how far the k nearest neighbours in the map are also near in the embedding space, 1.0 when
+    every one is among the k nearest there.  Returns {'trustworthiness', 'penalty_sum' (int), 'n', 'k', 'block'};
+    samples=True adds the device tensor 'penalty' [n] int32, each row's share.  Equal distances are ordered by index
+    (scikit-learn leaves them to its sort).  Raises ValueError unless 1 <= k < n / 2 (scikit-learn's rule), k <= 32
+    and n <= 65536, before any launch, and DadError when a row of emb or Y has a non-finite component."""
+    emb = _check_emb(emb)
+    n = emb.shape[0]
+    if not torch.is_tensor(Y) or Y.device != emb.device or Y.dtype != torch.float32 or tuple(Y.shape) != (n, 2):
+        raise ValueError("Y must be a float32 tensor [n, 2] on emb's device")
+    Y = Y.contiguous()
+    k = int(k)
+    if not 1 <= k <= _lib.KNN_MAX_K or 2 * k >= n or n > _lib.KNN_MAX_N:
+        raise ValueError("trustworthiness takes 1 <= k < n / 2, k <= %d and n <= %d, got n = %d, k = %d"
+                         % (_lib.KNN_MAX_K, _lib.KNN_MAX_N, n, k))
+    ws = _knn_workspace(n, k, emb.device)
+    out = torch.empty(_lib.TW_SLOTS, dtype=torch.float64, device=emb.device)
+    pen = torch.empty(n, dtype=torch.int32, device=emb.device) if samples else None
+    _enqueue_trustworthiness(emb, Y, k, out, pen, ws, _chunks)
+    o = out.cpu().numpy()
+    if int(o[_lib.TW_NONFINITE]) > 0:
+        raise _lib.DadError("dad_trustworthiness: %d row(s) of emb or Y have a non-finite component"
+                            % int(o[_lib.TW_NONFINITE]))
+    res = {"trustworthiness": float(o[_lib.TW_T]), "penalty_sum": int(o[_lib.TW_PENALTY]), "n": int(o[_lib.TW_N]),
+           "k": int(o[_lib.TW_K]), "block": o}
+    if samples:
+        res["penalty"] = pen
+    return res
+
+
+def neighbourhood_from_scores(initial, trained):
+    """The `initial_weights` / `trained_weights` / `improvement` block (the shape of separation_from_metrics) from two
+    {'noisy_knn_accuracy', 'noisy_to_clean_accuracy', 'clean_to_noisy_accuracy'} dicts (per cent); every value a
+    Python float."""
+    keys = ("noisy_knn_accuracy", "noisy_to_clean_accuracy", "clean_to_noisy_accuracy")
+    a = {k: float(initial[k]) for k in keys}
+    b = {k: float(trained[k]) for k in keys}
+    return {"initial_weights": a, "trained_weights": b,
+            "improvement": {k + "_change": b[k] - a[k] for k in keys}}
+
+
+def neighbourhood_report(initial_model, trained_model, clean_split, noisy_split, k=5):
+    """neighbourhood_from_scores under the initial and the trained weights: the noisy split's leave-one-out k-NN
+    accuracy (knn_store) and both retrieval accuracies across the domains (cross_domain_knn_store)."""
+    def scores(model):
+        cross = cross_domain_knn_store(model, clean_split, noisy_split, k)
+        return {"noisy_knn_accuracy": knn_store(model, noisy_split, k)["accuracy"],
+                "noisy_to_clean_accuracy": cross["noisy_to_clean"]["accuracy"],
+                "clean_to_noisy_accuracy": cross["clean_to_noisy"]["accuracy"]}
+    return neighbourhood_from_scores(scores(initial_model), scores(trained_model))
