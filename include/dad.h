@@ -58,7 +58,8 @@ extern "C" {
 #define DAD_T_CE 1
 #define DAD_T_KL 2
 #define DAD_T_ECDA 3
-#define DAD_T_SCL 4           /* always 0: C/train_CASIA.py:442, E/train_emodb.py:404 */
+#define DAD_T_SCL 4           /* dad_config.scl_on: the supervised-contrastive loss of this rank's batch; else 0, as
+                                 the reference hard-wires it (C/train_CASIA.py:442, E/train_emodb.py:404) */
 #define DAD_T_MSUM 5
 #define DAD_T_CLIPNORM 6
 #define DAD_T_CLIPCOEF 7
@@ -140,7 +141,23 @@ typedef struct dad_config {
                                    when every slab is live).  A set prepared ragged is read by a ragged step only
                                    (preparation ahead needs next_cfg->ragged == cfg->ragged).  0 = dense (the field
                                    was reserved[0], always 0, before) */
-  int32_t reserved[3];
+  /* The supervised-contrastive term (dad_scl below) in the step.  The three words were reserved[3], always 0, and
+   * stay addressable under that name: zeros mean what they meant, a step without the term.
+   *   scl_on   1: a post-warm-up step enqueues dad_scl's launches behind its tail launch, on the pre-dropout student
+   *            embeddings of the B clean rows (class yc) and of the Bn strong rows whose DACP mask is set (class =
+   *            the teacher's pseudo-label); it writes tail[DAD_T_SCL], adds w_scl dL/de to the step's dL/de and
+   *            w_scl L to the total loss.  The workspace grows by dad_scl's (dad_workspace_bytes counts it).
+   *            Each DP rank contrasts within its own batch; tail[DAD_T_SCL] is the local rank's value.
+   *   w_scl    TARGET_SCL_WEIGHT once the epoch reaches SCL_START_EPOCH
+   *   scl_tau  the temperature, > 0 and finite when scl_on (DAD_E_ARG otherwise) */
+  union {
+    int32_t reserved[3];
+    struct {
+      int32_t scl_on;
+      float w_scl;
+      float scl_tau;
+    };
+  };
 } dad_config;
 
 /* One clean + one noisy collated batch (I/dataload_noisy.py:124-129 format). */
@@ -199,7 +216,8 @@ typedef struct dad_state {
  * value when it loads the library, so a stale build fails at load instead of at a call. */
 int dad_abi_version(void);
 size_t dad_param_count(void);
-/* Step workspace bytes for cfg's geometry and precision (no initialisation needed). */
+/* Step workspace bytes for cfg's geometry and precision, plus dad_scl's workspace for B + Bn rows behind them when
+ * cfg->scl_on (no initialisation needed). */
 int dad_workspace_bytes(const dad_config* cfg, size_t* bytes);
 const char* dad_error_string(int code);
 /* Host-only planning of the 16-bit (FP16/BF16) encoder grid (no device call): teacher / student workgroups
@@ -770,6 +788,51 @@ int dad_trustworthiness(const float* emb, const float* Y, int64_t n, int k, doub
 int dad_trustworthiness_chunked(const float* emb, const float* Y, int64_t n, int k, double* out, int32_t* penalty,
                                 int chunks, void* workspace, void* stream);
 
+/* --- the supervised-contrastive loss and its gradient (csrc/scl.hip) ----------------------
+ * The reference names the term (SupervisedContrastiveLoss(temperature=0.1), TARGET_SCL_WEIGHT, SCL_START_EPOCH; "SCL -
+ * class alignment", C/model.py:74) but deleted its code and hard-wires 0 (C/train_CASIA.py:396,442), so this text is
+ * the definition: SupCon (Khosla et al. 2020, the "L_out" form) without a base-temperature factor.
+ *
+ * emb [n][256], labels [n], member [n] (a flag per row), tau > 0.  The member set A holds the flagged rows with a
+ * label in [0, 4) and |e_i| > 1e-12 (a row without a direction is left out: the normalisation's backward would
+ * otherwise be of order 1e12).  Rows outside A are left out by selection: their values, NaN included, reach no sum,
+ * and their gradient is 0.  With z_i = e_i / |e_i|, s_ia = z_i . z_a and P(i) = {p in A, p != i, y_p = y_i}:
+ *   l_i = -(1 / |P(i)|) sum_{p in P(i)} [ s_ip / tau - log sum_{a in A, a != i} exp(s_ia / tau) ]
+ *   L   = mean of l_i over the V anchors with |P(i)| >= 1;  L = 0 with a zero gradient when V = 0.
+ * Gradient, in closed form: p_ia = softmax over a != i of s_ia / tau, v_i = [|P(i)| >= 1], c_i = v_i / |P(i)|,
+ *   H_ia = (v_i p_ia - c_i [a in P(i)]) / (V tau),  G = H + H^T,  gz_i = sum_a G_ia z_a,
+ *   dL/de_i = (gz_i - z_i (z_i . gz_i)) / |e_i|.
+ * Two n x n passes over the Gram block of the unit rows on the fp32 matrix cores: the first takes each row's
+ * log-sum-exp under a running row maximum (no tau > 0 overflows or meets log 0) and its positives' sum, the second
+ * forms G tile by tile and accumulates G Z with MFMA; an epilogue applies the normalisation's backward.  The norms and
+ * the loss are reduced in double, the rest is fp32.  Enqueue-only on `stream` (graph-capturable), no floating-point
+ * atomics, every sum in a fixed order (two calls write bit-identical outputs), no counter or spin-wait between
+ * workgroups: the stream alone orders the four launches.  Rows past n are never read.
+ * out [DAD_SCL_SLOTS] floats (device); grad [n][256] (device, may be NULL: then only out is written).
+ * DAD_E_ARG: emb, labels, member, out or workspace is NULL, or tau is <= 0 or not finite (before anything is
+ * launched); DAD_E_SHAPE: n < 1 or n > DAD_SCL_MAX_N. */
+#define DAD_SCL_LOSS 0
+#define DAD_SCL_V 1               /* anchors: members whose class has another member */
+#define DAD_SCL_MEMBERS 2         /* |A| */
+#define DAD_SCL_ANCHORS 3         /* [4] anchors per class */
+#define DAD_SCL_NONFINITE 7       /* flagged rows (label in range) with a non-finite component (the block is then
+                                     meaningless) */
+#define DAD_SCL_SLOTS 8
+#define DAD_SCL_MAX_N 2048        /* largest n: 2 * DAD_MAX_BATCH, the step's largest batch */
+#define DAD_SCL_TILE 64           /* rows / columns of a tile of the pairwise passes */
+#define DAD_SCL_MAX_CHUNKS 8      /* most column chunks a row tile is split into */
+/* workspace bytes of dad_scl (0 for an unsupported n); no initialisation needed */
+size_t dad_scl_workspace_bytes(int64_t n);
+/* The grid of the two pairwise passes for n rows on a device of `cus` compute units, as dad_cluster_plan (one
+ * workgroup per compute unit).  Host only. */
+int dad_scl_plan(int64_t n, int cus, int* row_tiles, int* chunks, int* tiles_per_chunk);
+int dad_scl(const float* emb, const int64_t* labels, const uint8_t* member, int64_t n, float tau, float* out,
+            float* grad, void* workspace, void* stream);
+/* dad_scl with the chunk count asked for (clamped as dad_scl_plan clamps it; <= 0: the plan's), for tests of the
+ * chunked combination at small n. */
+int dad_scl_chunked(const float* emb, const int64_t* labels, const uint8_t* member, int64_t n, float tau, float* out,
+                    float* grad, int chunks, void* workspace, void* stream);
+
 /* --- the reference's helper types as operators (I/utils.py:317-652) -------------------
  * For trainer code that drives DataAugmentation / DACPManager / ECDALoss itself (the
  * train_step shim's callers, anchor calibration, I/train.py:334,341).  Same device functions
@@ -842,7 +905,8 @@ int dad_rng_draws(const dad_config* cfg, int which, uint64_t first, size_t n, fl
  * session is active: stop the first before starting another. */
 #define DAD_TK_ENCODE 0       /* dad_encode_ws[_f16] / dad_encode_f32 */
 #define DAD_TK_POOL 1         /* dad_pool */
-#define DAD_TK_TAIL 2         /* dad_tail_ecda_w / dad_tail_ecda (warm-up: dad_tail) */
+#define DAD_TK_TAIL 2         /* dad_tail_ecda_w / dad_tail_ecda (warm-up: dad_tail); with dad_config.scl_on also
+                                 dad_scl's four launches behind it */
 #define DAD_TK_WGRAD 3        /* dad_wgrad_direct (FP16/BF16) / dad_wgrad_f32 (FP32) */
 #define DAD_TK_REDUCE 4       /* dad_reduce_w (FP16/BF16) / dad_reduce (FP32) */
 #define DAD_TK_OPTIM 5        /* dad_optim */

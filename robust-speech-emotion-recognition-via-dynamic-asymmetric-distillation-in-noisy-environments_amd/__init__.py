@@ -15,7 +15,7 @@ from .model import EmotionClassifier, Emotion2VecEncoder, SSRLModel
 from .step import DADStep
 from .dist import DPComm, ProcessGroupComm
 from .data import DeviceLoader, FeatureStore
-from .utils import DACPManager, DataAugmentation, ECDALoss
+from .utils import DACPManager, DataAugmentation, ECDALoss, SupervisedContrastiveLoss
 from .trace import TrainingTrace
 from . import checkpoint, evaluate, pretrain
 from .evaluate import cluster_metrics, cluster_metrics_store, separation_report
@@ -25,7 +25,7 @@ from .evaluate import (cross_domain_knn_store, knn, knn_accuracy, knn_store, nei
                        trustworthiness)
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
-           "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "TrainingTrace",
+           "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "SupervisedContrastiveLoss", "TrainingTrace",
            "cluster_metrics", "cluster_metrics_store", "separation_report",
            "tsne", "tsne_affinities", "tsne_gradient", "tsne_store", "tsne_report",
            "domain_gap", "domain_gap_store", "enqueue_domain_gap_store", "alignment_report",

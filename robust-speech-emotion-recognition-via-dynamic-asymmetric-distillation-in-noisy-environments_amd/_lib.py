@@ -54,6 +54,10 @@ KNN_MAX_K, KNN_MAX_N, KNN_TILE, KNN_MAX_CHUNKS, KNN_WS_NONFINITE = 32, 65536, 64
 KV_CONFUSION, KV_QUERIES, KV_NO_VOTE, KV_SLOTS = 0, 32, 34, 40
 TW_T, TW_PENALTY, TW_N, TW_K, TW_VALID, TW_NONFINITE, TW_SLOTS = 0, 1, 2, 3, 4, 5, 8
 
+# result block of dad_scl (dad.h DAD_SCL_*): float32 slots ([4] anchors per class from SCL_ANCHORS on), limits
+SCL_LOSS, SCL_V, SCL_MEMBERS, SCL_ANCHORS, SCL_NONFINITE, SCL_SLOTS = 0, 1, 2, 3, 7, 8
+SCL_MAX_N, SCL_TILE, SCL_MAX_CHUNKS = 2048, 64, 8
+
 
 def ts_ld(n):
     """dad.h DAD_TS_LD: the row stride of P."""
@@ -92,6 +96,19 @@ class DadConfig(ctypes.Structure):
         ("splits", ctypes.c_int32), ("prepped", ctypes.c_int32), ("ragged", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 3),
     ]
+
+
+def _reserved_word(index, ctype):
+    off = DadConfig.reserved.offset + 4 * index
+    return property(lambda self: ctype.from_buffer(self, off).value,
+                    lambda self, v: setattr(ctype.from_buffer(self, off), "value", v))
+
+
+# dad.h overlays the three reserved words with the supervised-contrastive term's fields (an anonymous union:
+# `reserved` stays addressable, and zeros there still mean a step without the term).  The same overlay here.
+DadConfig.SCL_FIELDS = (("scl_on", ctypes.c_int32), ("w_scl", ctypes.c_float), ("scl_tau", ctypes.c_float))
+for _i, (_name, _ctype) in enumerate(DadConfig.SCL_FIELDS):
+    setattr(DadConfig, _name, _reserved_word(_i, _ctype))
 
 
 class DadBatch(ctypes.Structure):
@@ -269,6 +286,14 @@ EXPORTS = {
     "dad_trustworthiness_chunked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_void_p]),
+    "dad_scl_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "dad_scl_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                    ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "dad_scl": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_scl_chunked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                       ctypes.c_void_p, ctypes.c_void_p]),
     "dad_timing_start": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "dad_timing_kernels": (ctypes.c_int, [ctypes.c_uint]),
     "dad_timing_reset": (ctypes.c_int, []),
@@ -290,7 +315,8 @@ OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_step_plan_kernels", "dad_trace_
                     "dad_tsne_gradient", "dad_tsne_plan", "dad_tsne_gradient_chunked", "dad_tsne_run",
                     "dad_domain_gap_workspace_bytes", "dad_domain_gap_plan", "dad_domain_gap",
                     "dad_domain_gap_chunked", "dad_knn_workspace_bytes", "dad_knn_plan", "dad_knn", "dad_knn_chunked",
-                    "dad_knn_vote", "dad_trustworthiness", "dad_trustworthiness_chunked")
+                    "dad_knn_vote", "dad_trustworthiness", "dad_trustworthiness_chunked",
+                    "dad_scl_workspace_bytes", "dad_scl_plan", "dad_scl", "dad_scl_chunked")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

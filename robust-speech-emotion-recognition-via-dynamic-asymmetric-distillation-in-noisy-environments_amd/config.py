@@ -27,6 +27,9 @@ _COMMON = dict(
     FINAL_CONSISTENCY_WEIGHT=0.3, WEIGHT_RAMP_EPOCHS=30, GRADIENT_CLIPPING=True,
     MAX_GRAD_NORM=1.0, USE_DACP=True, USE_ECDA=True, LEARNING_RATE_SCHEDULER="cosine",
     ANCHOR_STD_K=1.5, BATCH_SIZE=64,
+    # the supervised-contrastive term: the reference keeps the two switches (off) in all three configs
+    # (I/config.py, C/config_casia.py, E/config_emodb.py) and deleted SupervisedContrastiveLoss(temperature=0.1)
+    TARGET_SCL_WEIGHT=0.0, SCL_START_EPOCH=5001, SCL_TEMPERATURE=0.1,
 )
 # per-dataset defaults (I/config.py:60-123, C/config_casia.py:63-126, E/config_emodb.py:63-126)
 FLAVOR_DEFAULTS = {
@@ -119,6 +122,13 @@ class ConfigView:
             w_ecda = 0.0
         return w_kl, w_ecda, False
 
+    def scl_weight(self, epoch):
+        """The supervised-contrastive term's weight: 0 in the warm-up (CE only) and before SCL_START_EPOCH, then
+        TARGET_SCL_WEIGHT (the reference keeps the two switches and no ramp)."""
+        if epoch < self.WARMUP_EPOCHS or epoch < self.SCL_START_EPOCH:
+            return 0.0
+        return self.TARGET_SCL_WEIGHT
+
     def lr_at(self, epoch):
         """CosineAnnealingLR(T_max=EPOCHS) after `epoch` scheduler steps (I/train.py:363,519)."""
         if getattr(self, "LEARNING_RATE_SCHEDULER", "cosine") != "cosine":
@@ -147,6 +157,9 @@ def dad_config_for(view, Bc, Tc, Bn, Tn, epoch, adam_step, lr=None, precision=_l
     c.ecda_on = int(use_ecda and w_ecda > 0)
     c.dp_world = int(dp_world)
     c.w_kl, c.w_ecda = w_kl, w_ecda
+    w_scl = view.scl_weight(epoch)
+    if w_scl > 0:               # (off: the three words stay zero, as the reserved words they were)
+        c.scl_on, c.w_scl, c.scl_tau = 1, w_scl, view.SCL_TEMPERATURE
     gamma = view.DACP_QUANTILE_START + (view.DACP_QUANTILE_END - view.DACP_QUANTILE_START) * (epoch / view.EPOCHS)
     c.dacp_gamma = gamma
     a = view.DACP_THRESHOLD_SMOOTHING_ALPHA
@@ -194,6 +207,7 @@ CONFIG_KEYS = (
     "ECDA_COMPACTNESS_WEIGHT_GAMMA", "ECDA_REPULSION_WEIGHT_DELTA", "LABEL_SMOOTHING_FACTOR",
     "USE_LABEL_SMOOTHING", "DROPOUT_RATE", "WEAK_NOISE_STD", "STRONG_NOISE_STD", "TEMPORAL_MASK_RATIO",
     "GRADIENT_CLIPPING", "MAX_GRAD_NORM", "WEIGHT_DECAY", "EMA_MOMENTUM", "DACP_QUALITY_SMOOTHING_BETA",
+    "TARGET_SCL_WEIGHT", "SCL_START_EPOCH", "SCL_TEMPERATURE",
 )
 
 

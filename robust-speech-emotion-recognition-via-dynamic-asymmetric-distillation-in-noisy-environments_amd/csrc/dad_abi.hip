@@ -217,6 +217,7 @@ DadReduceArgs reduce_args(const Step& s) {
   ra.g = s.G; ra.warmup = cfg->warmup;
   ra.want_norm = cfg->dp_world == 1;
   ra.w_kl = cfg->w_kl; ra.w_ecda = cfg->w_ecda;
+  ra.w_scl = s.plan.scl_n ? cfg->w_scl : 0.0f;
   ra.ge_ecda = s.ws.ge_ecda;
   ra.gzb = s.ws.gzb; ra.eflag = s.ws.eflag; ra.student = s.st->student; ra.emb = s.st->emb;
   if (s.explicit_rng()) { ra.keep1 = s.bt->keep1; ra.keep2 = s.bt->keep2; }
@@ -241,6 +242,27 @@ int launch_wgrad(const Step& s, hipStream_t stream, const DadPrepArgs& next_clea
   const StepPlan& p = s.plan;
   if (kStepKernels[p.wgrad].sig == SIG_WGRAD_CP) return launch(p.wgrad, p.wgrad_grid, stream, wgrad_args(s), ra, next_clean);
   return launch(p.wgrad, p.wgrad_grid, stream, wgrad_args(s), ra);
+}
+
+// The workspace of a step: dad_ws_layout's regions, then (dad_config.scl_on) dad_scl's workspace for the Bc + Bn
+// rows, so a step without the term has the layout and the size it had.
+size_t step_ws_bytes(const dad_config* cfg) {
+  const size_t base = dad_ws_layout(geom_of(cfg), max_splits_of(cfg), cfg->precision).bytes;
+  return cfg->scl_on ? dad_align(base) + scl_ws_bytes(cfg->B + (cfg->Bn > 0 ? cfg->Bn : 0)) : base;
+}
+
+// 3b. the supervised-contrastive term on what the tail launch left: the clean rows with their labels and the strong
+//     rows the DACP mask lets in with the teacher's pseudo-labels; the loss into the tail buffer, w_scl dL/de into
+//     the ECDA rows of dL/de (flagging the rows it writes, as ECDA does: the fused weight gradient adds flagged rows)
+int launch_scl(const Step& s, void* workspace, hipStream_t stream) {
+  const dad_config* cfg = s.cfg;
+  const int B = s.G.Bc, Bn = s.G.Bn;
+  float* tail = s.st->tail;
+  const SclSrc src{s.st->emb, s.bt->yc, nullptr, B,
+                   s.st->emb + (size_t)(B + Bn) * DAD_H, tail + DAD_TAIL_HDR + Bn, tail + DAD_TAIL_HDR + 2 * Bn, Bn};
+  const SclDst dst{nullptr, tail + DAD_T_SCL, nullptr, s.ws.ge_ecda, s.ws.eflag, cfg->w_scl};
+  const size_t off = dad_align(dad_ws_layout(s.G, s.plan.max_splits, cfg->precision).bytes);
+  return scl_enqueue(src, dst, cfg->scl_tau, s.plan.scl, ws_ptr<char>(workspace, off), stream);
 }
 
 }  // namespace
@@ -331,7 +353,7 @@ int dad_workspace_bytes(const dad_config* cfg, size_t* bytes) {
   int rc = check_cfg(cfg);
   if (rc) return rc;
   if (!bytes) return DAD_E_ARG;
-  *bytes = dad_ws_layout(geom_of(cfg), max_splits_of(cfg), cfg->precision).bytes;
+  *bytes = step_ws_bytes(cfg);
   return DAD_OK;
 }
 
@@ -393,6 +415,7 @@ static int step_compute_phases(const dad_config* cfg, const dad_batch* bt, const
     if (plan.tail_prep) { in_tail = next; prep_only(in_tail, plan.tail_prep); }
   }
   DAD_RET(launch_tail(s, stream, in_tail, pa));
+  if (plan.scl_n) DAD_RET(launch_scl(s, workspace, stream));   // (timed with the tail: DAD_TK_TAIL)
   tk_mark(TK_TAIL, stream);
   const DadReduceArgs ra = reduce_args(s);
   DAD_RET(launch_wgrad(s, stream, in_wgrad, ra));

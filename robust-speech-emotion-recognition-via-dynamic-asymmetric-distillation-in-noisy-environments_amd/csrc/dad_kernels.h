@@ -167,6 +167,7 @@ struct DadReduceArgs {
   const float* tailf;
   float* grad; float* normpart;
   const uint32_t* pool_abort;   // fused pooling: this step's abort word (DAD_POOL_ABORT), else NULL
+  float w_scl;                  // weight of tailf[DAD_T_SCL] in the total (0 without the term; last: nothing above moves)
 };
 
 struct DadOptimArgs {

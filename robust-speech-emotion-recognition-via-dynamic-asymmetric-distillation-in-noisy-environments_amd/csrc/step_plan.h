@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "dad_kernels.h"
+#include "scl.h"
 
 inline int check_cfg(const dad_config* c) {
   if (!c) return DAD_E_ARG;
@@ -21,8 +22,12 @@ inline int check_cfg(const dad_config* c) {
   if (c->rng_mode != DAD_RNG_EXPLICIT && c->rng_mode != DAD_RNG_COUNTER) return DAD_E_ARG;
   if (c->dp_world < 1) return DAD_E_ARG;
   if (c->ragged && !dad_prec16(c->precision)) return DAD_E_UNSUPPORTED;   // (ragged mode: the 16-bit store-fed steps)
+  if (c->scl_on && !(scl_tau_ok(c->scl_tau) && c->w_scl >= -3.402823466e38f && c->w_scl <= 3.402823466e38f)) return DAD_E_ARG;
   return DAD_OK;
 }
+
+// the step runs the supervised-contrastive term: switched on, and past the warm-up (which is CE only)
+inline bool scl_in_step(const dad_config* c) { return c->scl_on && !c->warmup; }
 
 inline DadGeom geom_of(const dad_config* c) { return dad_geom(c->B, c->T, c->Bn, c->Tn); }
 
@@ -205,6 +210,10 @@ struct StepPlan {
   StepKernel tail;
   int tail_grid;
   int tail_prep;                // DAD_PREP_* parts of the NEXT batch the tail launch prepares
+  // the supervised-contrastive term's four launches (scl.hip), between the tail and the weight gradient; scl_n = 0:
+  // not made.  Not among the DAD_STEP_LAUNCHES dad_step_plan_kernels lists: dad_scl_plan reports this grid.
+  int scl_n;
+  SclPlan scl;
   StepKernel wgrad;
   int wgrad_grid, wgrad_tiles;
   int wgrad_clean, wgrad_store;    // it converts the next batch's clean rows; through that batch's store table
@@ -285,6 +294,12 @@ inline StepPlan plan_step(const dad_config* cfg, const dad_batch* batch, const d
   // (the `_s16` tail: when the rows it prepares lie in a 16-bit store)
   if (tail_w && ragged) p.tail = K_TAIL_ECDA_W_RG;
   else if (p.tail_prep && rows_need_s16(next_cfg, next_batch, p.tail_prep)) p.tail = K_TAIL_ECDA_W_S16;
+
+  // the supervised-contrastive term: the clean rows and the strong rows as one set of Bc + Bn
+  if (scl_in_step(cfg)) {
+    p.scl_n = G.Bc + Bn;
+    p.scl = scl_plan_of(p.scl_n, cus);
+  }
 
   // weight gradient and the split sums.  16-bit: WGD_NDB column blocks per split, the grid a
   // multiple of 8 (XCD-aware tile order) with WGD_XWG spare workgroups for the reduce's extra blocks.

@@ -170,7 +170,8 @@ __device__ double extra_block_t(const DadReduceArgs& a, int e, int tid, float (*
     // a pooling timeout in the tail launch (DAD_POOL_ABORT): NaN total, so dad_optim (on every DP
     // rank, after the all-reduce) skips this step's update
     const bool abort = a.pool_abort != nullptr && __hip_atomic_load(a.pool_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-    ex[12] = abort ? __builtin_nanf("") : ce + a.w_kl * kl + a.w_ecda * ecda_l;
+    // (the supervised-contrastive term: written behind the tail launch by dad_scl_final; without it 0 * 0)
+    ex[12] = abort ? __builtin_nanf("") : ce + a.w_kl * kl + a.w_ecda * ecda_l + a.w_scl * tf[DAD_T_SCL];
     ex[13] = ce;
     ex[14] = kl;
     ex[15] = ecda_l;

@@ -206,6 +206,7 @@ class DADStep:
         self._bufs = {}
         self._prepped_key = None       # identity of the batch the last step's tail launch prepared
         self.last_prepped = False
+        self._last_scl_on = False      # the last step ran the supervised-contrastive term (losses())
         self._ahead = None             # the last step's (*prepped, *pending) out-parameters (last_ahead)
         self._next_keep = None
         self._shadow_dirty = False
@@ -311,8 +312,10 @@ class DADStep:
 
     def _workspace(self, cfg):
         # dad_workspace_bytes depends on the geometry, the split count, the precision and the
-        # warm-up flag only (dad_abi.hip: dad_ws_layout(geom_of, max_splits_of, precision))
-        key = (cfg.B, cfg.T, cfg.Bn, cfg.Tn, cfg.splits, cfg.precision, cfg.warmup)
+        # warm-up flag (dad_abi.hip: dad_ws_layout(geom_of, max_splits_of, precision)), and on scl_on, whose
+        # region lies behind every other one: a larger buffer takes over the old one's contents, so rows the
+        # last step prepared ahead stay where this step looks for them
+        key = (cfg.B, cfg.T, cfg.Bn, cfg.Tn, cfg.splits, cfg.precision, cfg.warmup, cfg.scl_on)
         need = self._ws_need.get(key)
         if need is None:
             nbytes = ctypes.c_size_t(0)
@@ -320,7 +323,9 @@ class DADStep:
             need = self._ws_need[key] = int(nbytes.value)
         if self._ws is None or self._ws.numel() < need:
             # zero-filled once (finite bytes everywhere; the step needs no initialisation)
-            self._ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            old, self._ws = self._ws, torch.zeros(need, dtype=torch.uint8, device=self.device)
+            if old is not None and cfg.scl_on:
+                self._ws[:old.numel()].copy_(old)
         return self._ws
 
     # ------------------------------------------------------------------------------- step
@@ -349,6 +354,7 @@ class DADStep:
         st = self._state_struct(cfg.Bn, cfg.B)
         self._loss_vec = torch.empty(4, device=self.device)     # written by the optimizer/commit kernel
         st.losses = self._loss_vec.data_ptr()
+        self._last_scl_on = bool(cfg.scl_on) and not cfg.warmup    # (this step writes tail[DAD_T_SCL])
         self._keepalive = keep
         return cfg, bt, st
 
@@ -563,11 +569,15 @@ class DADStep:
         return out
 
     def losses(self):
-        """Loss dict of the last step (keys of I/train.py:468-470 + scl_loss for CASIA/EMODB)."""
+        """Loss dict of the last step (keys of I/train.py:468-470 + scl_loss for CASIA/EMODB; for IEMOCAP, whose
+        trainer has no such key, only while the term's weight is positive).  scl_loss is this rank's value
+        (tail[DAD_T_SCL]); it is 0 when the term is off, as the reference hard-wires it (C/train_CASIA.py:442)."""
         g = self._loss_vec       # fresh per step: no copy kernels, no host sync
         out = {"total_loss": g[0], "supervised_ce_loss": g[1], "consistency_loss": g[2], "ecda_loss": g[3]}
-        if self.view.flavor in ("casia", "emodb"):
-            out["scl_loss"] = torch.zeros((), device=self.device)   # always 0 (C/train_CASIA.py:442)
+        on = self._last_scl_on
+        if on or self.view.flavor in ("casia", "emodb"):
+            # (a copy: the tail buffer is the next step's too)
+            out["scl_loss"] = self._last["tail"][_lib.T_SCL].clone() if on else torch.zeros((), device=self.device)
         return out
 
     def range_flag(self, clear=False):

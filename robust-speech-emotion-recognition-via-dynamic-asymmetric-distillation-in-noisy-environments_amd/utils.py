@@ -14,6 +14,8 @@ classes, constructors, methods and fields here:
         .ema_thresholds, .class_quality_scores, .batch_scores_per_class
     ECDALoss()(clean_feats, noisy_feats, clean_labels, noisy_labels,
                noisy_mask, noisy_scores, class_weights_wce)                       dad_ecda_loss
+    SupervisedContrastiveLoss(temperature=0.1)(features, labels, mask=None)       dad_scl
+        (the type C/train_CASIA.py and E/train_emodb.py constructed before the reference deleted it)
 
 Every operator is a HIP kernel behind the C ABI (include/dad.h), running the device
 functions of the fused step; tensors must be on the GPU.  Config is read at call time
@@ -308,3 +310,49 @@ class ECDALoss(torch.nn.Module):
                                             gc.data_ptr(), gn.data_ptr(), ws.data_ptr(), _stream(ec)),
                    "dad_ecda_loss")
         return _EcdaFn.apply(clean_feats, noisy_feats, loss, gc, gn)
+
+
+class _SclFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, loss, grad):
+        ctx.save_for_backward(grad)
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+class SupervisedContrastiveLoss(torch.nn.Module):
+    """The type the reference's trainers constructed as `SupervisedContrastiveLoss(temperature=0.1)` before it
+    deleted the class and hard-wired the term to 0 (C/train_CASIA.py:396,442).  The loss is the one include/dad.h
+    defines for dad_scl: SupCon ("L_out", no base-temperature factor) over the rows whose `mask` is set (default:
+    all), whose label lies in [0, 4) and whose norm exceeds 1e-12, on the L2-normalised rows; differentiable w.r.t.
+    `features` [n][256].  `last_stats` holds the device block of the last call (_lib.SCL_* slots)."""
+
+    def __init__(self, temperature=0.1):
+        super().__init__()
+        self.temperature = float(temperature)
+        self.last_stats = None
+
+    def forward(self, features, labels, mask=None):
+        _need_cuda(features, "SupervisedContrastiveLoss features")
+        fn = _lib.require("dad_scl", "SupervisedContrastiveLoss")
+        dev = features.device
+        if features.dim() != 2 or features.shape[1] != 256:
+            raise ValueError("features must be [n][256] (HIDDEN_DIM)")
+        n = features.shape[0]
+        e = features.detach().contiguous().float()
+        y = labels.to(dev, torch.int64).contiguous()
+        m = (torch.ones(n, dtype=torch.uint8, device=dev) if mask is None
+             else (mask.to(dev) != 0).contiguous().view(torch.uint8))
+        if y.numel() != n or m.numel() != n:
+            raise ValueError("labels and mask must have one entry per row of features")
+        out = torch.empty(_lib.SCL_SLOTS, device=dev)
+        grad = torch.empty_like(e)
+        ws = torch.empty(int(_lib.lib().dad_scl_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+        _lib.check(fn(e.data_ptr(), y.data_ptr(), m.data_ptr(), n, self.temperature, out.data_ptr(), grad.data_ptr(),
+                      ws.data_ptr(), _stream(e)), "dad_scl")
+        self.last_stats = out
+        return _SclFn.apply(features, out[_lib.SCL_LOSS], grad)
