@@ -524,6 +524,104 @@ size_t dad_eval_workspace_bytes(int64_t n, int64_t slabs, int precision, int wit
  * slabs outside [0, n * 2^26]; DAD_E_UNSUPPORTED: DAD_PREC_BF16. */
 int dad_eval_split(const dad_eval_args* args, void* workspace, void* stream);
 
+/* --- windows of a split: emotion over time, store-fed (csrc/eval_windows.hip) -------------
+ * dad_eval_split answers once per utterance.  dad_eval_windows classifies every sliding window, or every
+ * prefix, of every utterance of a split in one pass over the store: the encoder is frame-wise, so a window's
+ * embedding is a partial sum of the per-frame rows relu(W1 x_t + b1) that the split evaluator already computes.
+ * By definition a window's outputs are SSRLModel.predict / get_embeddings (I/model.py:225-265) on the
+ * utterance's features cropped to the window.
+ *
+ * Utterance i has L = lens[i] frames; the hop is h = hop >= 1 frames and the span m = span >= 1 hops.
+ *   S = ceil(L / h) hop-segments; segment s is frames [s h, min((s + 1) h, L)).
+ *   DAD_WIN_SLIDING  J = 0 if L = 0, else max(1, S - m + 1); window j is frames [j h, min((j + m) h, L)).  The
+ *                    last window ends at L; an utterance shorter than m h has one window, itself.
+ *   DAD_WIN_PREFIX   J = S; window j is frames [0, min((j + 1) h, L)).  span must be 1 (DAD_E_ARG otherwise).
+ *                    The last prefix is the whole utterance.
+ * For a window of c frames: embedding = (sum over its frames of relu(W1 x_t + b1)) / c; logits, softmax
+ * probabilities, certainty score and first-maximum argmax by dad_predict_head's / dad_eval_split's arithmetic.
+ * Windows are laid out ragged: win_off[n + 1] is the exclusive prefix of J and `windows` = win_off[n].
+ *
+ * The encoder sums the rows per piece: a maximal run of frames inside one 32-frame slab and one hop-segment.
+ * An utterance's pieces, in frame order, are cut at every multiple of 32 and of h below L (a slab holds at most
+ * min(32, ceil(32 / h) + 1) of them); piece_off[n + 1] is the exclusive prefix of their number,
+ * ceil(L / 32) + ceil(L / h) - ceil(L / lcm(32, h)), and `pieces` = piece_off[n].  A window's sum is the
+ * left-to-right fp32 sum of its pieces from 0, as dad_eval_split sums slab partials; SLIDING re-sums every
+ * window's pieces (no subtraction of running sums), so for h % 32 == 0 the last PREFIX window equals
+ * dad_eval_split's emb / logits / pred bit for bit, and SLIDING (h, 1) and PREFIX (h, 1) agree bit for bit on
+ * window 0.  Both prefixes are pure host functions of (lens, hop, span, mode).  win_off_host is the HOST copy
+ * of win_off: the entry point reads its first and last entries to hold `windows` to it before anything is
+ * launched (DAD_E_ARG).  An utterance whose device entries disagree with its length is treated as J = 0.
+ * windows and pieces must be below 2^31 (DAD_E_SHAPE).
+ *
+ * Per-utterance outputs; for an utterance with J = 0 every integer output is -1 and mean_probs is 0:
+ *   mean_probs [n][4]  the window probabilities summed in window order in fp32, / J
+ *   mean_pred [n]      first-maximum argmax of mean_probs
+ *   vote_pred [n]      the class most windows predict, ties to the lowest class index
+ *   last_pred [n]      w_pred of the last window
+ *   settle [n]         the smallest j such that every window j' >= j predicts last_pred
+ *   switches [n]       the number of j >= 1 with w_pred[j] != w_pred[j - 1]
+ * Result block: result[DAD_EW_SLOTS] int64 (exact). */
+#define DAD_WIN_SLIDING 0
+#define DAD_WIN_PREFIX 1
+#define DAD_EW_CONF_MEAN 0      /* [4][4] row = label, column = mean_pred, over labelled utterances with J > 0 */
+#define DAD_EW_CONF_VOTE 16     /* the same for vote_pred */
+#define DAD_EW_CONF_LAST 32     /* the same for last_pred */
+#define DAD_EW_N 48             /* n */
+#define DAD_EW_N_LABELLED 49    /* utterances with a label in [0, 4) */
+#define DAD_EW_N_EMPTY 50       /* utterances with J = 0 */
+#define DAD_EW_N_WINDOWS 51     /* windows */
+#define DAD_EW_N_NONFINITE 52   /* windows with a logit that is not finite */
+#define DAD_EW_SETTLE_SUM 53    /* over utterances with J > 0: sum of settle */
+#define DAD_EW_SWITCHES_SUM 54  /* sum of switches */
+#define DAD_EW_SETTLE_FRAMES_SUM 55 /* sum of the exclusive end frame of window `settle` */
+#define DAD_EW_CURVE 64         /* curve slots: window index j < 64 (56..63 reserved, written 0) */
+#define DAD_EW_REACHED 64       /* [64] labelled utterances with J > j */
+#define DAD_EW_CORRECT 128      /* [64] those of them with w_pred[j] == label */
+#define DAD_EW_CARRIED 192      /* [64] labelled utterances with J > 0 whose w_pred[min(j, J - 1)] == label */
+#define DAD_EW_SLOTS 256
+/* Rows as dad_eval_args (store, rows, lens, labels, slab_off, slabs).  One network per call: params is the
+ * student's or the teacher's flat vector.  Optional outputs: NULL = not written.  Enqueue only, no allocation,
+ * no device read on the host, no floating-point atomics: two calls on the same inputs write the same bits. */
+typedef struct dad_window_args {
+  const void* store;            /* [frames][768], dtype store_dtype */
+  const int64_t* rows;          /* [n] store row of frame 0 */
+  const int32_t* lens;          /* [n] frames */
+  const int64_t* labels;        /* [n] or NULL */
+  const int32_t* slab_off;      /* [n + 1] exclusive prefix of ceil(lens / 32) */
+  const float* params;          /* [DAD_NPARAM] flat [W1|b1|W2|b2] */
+  const int32_t* win_off;       /* [n + 1] device: exclusive prefix of J */
+  const int32_t* piece_off;     /* [n + 1] device: exclusive prefix of the piece counts */
+  const int32_t* win_off_host;  /* [n + 1] HOST copy of win_off */
+  float* w_emb;                 /* [windows][256] */
+  float* w_logits;              /* [windows][4] */
+  float* w_probs;               /* [windows][4] */
+  float* w_score;               /* [windows] certainty score (dad_predict_head's) */
+  int64_t* w_pred;              /* [windows] first-maximum argmax */
+  float* mean_probs;            /* [n][4] */
+  int64_t* mean_pred;           /* [n] */
+  int64_t* vote_pred;           /* [n] */
+  int64_t* last_pred;           /* [n] */
+  int32_t* settle;              /* [n] */
+  int32_t* switches;            /* [n] */
+  int64_t* result;              /* [DAD_EW_SLOTS], required */
+  int64_t n;                    /* utterances, >= 1 */
+  int64_t slabs;                /* slab_off[n] */
+  int64_t windows;              /* win_off[n] */
+  int64_t pieces;               /* piece_off[n] */
+  int32_t hop;                  /* frames, >= 1 */
+  int32_t span;                 /* hops, >= 1 */
+  int32_t mode;                 /* DAD_WIN_* */
+  int32_t store_dtype;          /* DAD_STORE_* */
+  int32_t use_entropy;          /* USE_ENTROPY_IN_SCORE */
+  int32_t precision;            /* DAD_PREC_FP32 (exact-f32 MFMA) or DAD_PREC_FP16 (rows and W1 rounded to fp16) */
+} dad_window_args;
+/* workspace bytes of dad_eval_windows (0 for unsupported sizes); no initialisation needed */
+size_t dad_eval_windows_workspace_bytes(int64_t n, int64_t slabs, int64_t windows, int64_t pieces, int precision);
+/* DAD_E_ARG: a required pointer is NULL, an unknown dtype / precision / mode, hop < 1, span < 1, PREFIX with
+ * span != 1, or windows != win_off_host[n]; DAD_E_SHAPE: n < 1, slabs outside [0, n * 2^26], windows or pieces
+ * outside [0, 2^31) or pieces < slabs; DAD_E_UNSUPPORTED: DAD_PREC_BF16.  Nothing is launched on an error. */
+int dad_eval_windows(const dad_window_args* args, void* workspace, void* stream);
+
 /* --- class separation of a split's embeddings (csrc/cluster.hip) -------------------------
  * calculate_cluster_metrics (I/iemocap_plot_tsne.py:390-398): scikit-learn's silhouette_score and
  * calinski_harabasz_score of emb [n][256] (dad_eval_split's emb / t_emb) under labels [n], whose

@@ -23,6 +23,8 @@ from .evaluate import tsne, tsne_affinities, tsne_gradient, tsne_report, tsne_st
 from .evaluate import alignment_report, domain_gap, domain_gap_store, enqueue_domain_gap_store
 from .evaluate import (cross_domain_knn_store, knn, knn_accuracy, knn_store, neighbourhood_report,
                        trustworthiness)
+from .evaluate import (duration_report, early_decision_curve, enqueue_eval_windows, evaluate_windows_store,
+                       window_frames, windows, windows_host)
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
            "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "SupervisedContrastiveLoss", "TrainingTrace",
@@ -30,6 +32,8 @@ __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "D
            "tsne", "tsne_affinities", "tsne_gradient", "tsne_store", "tsne_report",
            "domain_gap", "domain_gap_store", "enqueue_domain_gap_store", "alignment_report",
            "knn", "knn_accuracy", "knn_store", "cross_domain_knn_store", "trustworthiness", "neighbourhood_report",
+           "windows", "windows_host", "window_frames", "enqueue_eval_windows", "evaluate_windows_store",
+           "early_decision_curve", "duration_report",
            "build", "lib"]
 
 

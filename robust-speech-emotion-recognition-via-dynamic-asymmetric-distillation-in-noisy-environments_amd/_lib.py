@@ -73,6 +73,13 @@ EV_CONF_STUDENT, EV_CONF_TEACHER, EV_DISAGREE, EV_N, EV_N_LABELLED, EV_N_SKIPPED
 EV_COUNTS = 40
 EV_MOMENTS, EV_M_COUNT, EV_M_MEAN, EV_M_VAR = 3, 0, 1, 2
 
+# dad_eval_windows (dad.h DAD_WIN_*, DAD_EW_*): modes, the int64 slots of the result block
+WIN_SLIDING, WIN_PREFIX = 0, 1
+EW_CONF_MEAN, EW_CONF_VOTE, EW_CONF_LAST = 0, 16, 32
+EW_N, EW_N_LABELLED, EW_N_EMPTY, EW_N_WINDOWS, EW_N_NONFINITE = 48, 49, 50, 51, 52
+EW_SETTLE_SUM, EW_SWITCHES_SUM, EW_SETTLE_FRAMES_SUM = 53, 54, 55
+EW_CURVE, EW_REACHED, EW_CORRECT, EW_CARRIED, EW_SLOTS = 64, 64, 128, 192, 256
+
 
 class DadConfig(ctypes.Structure):
     _fields_ = [
@@ -146,6 +153,15 @@ class DadEvalArgs(ctypes.Structure):
                   "score", "pred", "t_emb", "t_logits", "t_pred", "counts", "moments")]
                 + [("n", ctypes.c_int64), ("slabs", ctypes.c_int64), ("store_dtype", ctypes.c_int32),
                    ("use_entropy", ctypes.c_int32), ("precision", ctypes.c_int32), ("reserved", ctypes.c_int32)])
+
+
+class DadWindowArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_void_p) for n in
+                 ("store", "rows", "lens", "labels", "slab_off", "params", "win_off", "piece_off", "win_off_host",
+                  "w_emb", "w_logits", "w_probs", "w_score", "w_pred", "mean_probs", "mean_pred", "vote_pred",
+                  "last_pred", "settle", "switches", "result")]
+                + [(n, ctypes.c_int64) for n in ("n", "slabs", "windows", "pieces")]
+                + [(n, ctypes.c_int32) for n in ("hop", "span", "mode", "store_dtype", "use_entropy", "precision")])
 
 
 class DadTsneArgs(ctypes.Structure):
@@ -225,6 +241,9 @@ EXPORTS = {
                                         ctypes.c_void_p]),
     "dad_eval_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     "dad_eval_split": (ctypes.c_int, [ctypes.POINTER(DadEvalArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_eval_windows_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                           ctypes.c_int64, ctypes.c_int]),
+    "dad_eval_windows": (ctypes.c_int, [ctypes.POINTER(DadWindowArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "dad_augment": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -316,7 +335,8 @@ OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_step_plan_kernels", "dad_trace_
                     "dad_domain_gap_workspace_bytes", "dad_domain_gap_plan", "dad_domain_gap",
                     "dad_domain_gap_chunked", "dad_knn_workspace_bytes", "dad_knn_plan", "dad_knn", "dad_knn_chunked",
                     "dad_knn_vote", "dad_trustworthiness", "dad_trustworthiness_chunked",
-                    "dad_scl_workspace_bytes", "dad_scl_plan", "dad_scl", "dad_scl_chunked")
+                    "dad_scl_workspace_bytes", "dad_scl_plan", "dad_scl", "dad_scl_chunked",
+                    "dad_eval_windows_workspace_bytes", "dad_eval_windows")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

@@ -30,13 +30,13 @@
 
 #include "dad_common.h"
 #include "dad_kernels.h"
+#include "eval_rows.h"   // row loaders, the slab GEMM loop and epilogue, the head arithmetic (shared with eval_windows.hip)
 
 namespace {
 
 constexpr int kEncThreads = 256;     // 4 waves, one slab each
 constexpr int kHeadWaves = 4;
 constexpr int kResThreads = 256;
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 struct EvalEncArgs {
   const void* store;
@@ -63,172 +63,6 @@ struct EvalResArgs {
   const int32_t* pred_s; const int32_t* pred_t; const float* score; const int32_t* bad;
   int64_t* counts; double* moments;
 };
-
-// ---- store rows: 4 (fp32 path) or 8 (fp16 path) consecutive channels of one row ---------------
-template <int DT> struct Raw4;
-template <> struct Raw4<DAD_STORE_F32> {
-  f32x4 v;
-  __device__ __forceinline__ void load(const void* base, size_t el) { v = *reinterpret_cast<const f32x4*>((const float*)base + el); }
-  __device__ __forceinline__ f32x4 get() const { return v; }
-};
-// halves one scalar at a time, as collate.hip widens them
-template <> struct Raw4<DAD_STORE_F16> {
-  u32x2 v;
-  __device__ __forceinline__ void load(const void* base, size_t el) { v = *reinterpret_cast<const u32x2*>((const uint16_t*)base + el); }
-  static __device__ __forceinline__ float h(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
-  __device__ __forceinline__ f32x4 get() const {
-    f32x4 r;
-    r[0] = h(v[0] & 0xffffu); r[1] = h(v[0] >> 16); r[2] = h(v[1] & 0xffffu); r[3] = h(v[1] >> 16);
-    return r;
-  }
-};
-template <> struct Raw4<DAD_STORE_BF16> {
-  u32x2 v;
-  __device__ __forceinline__ void load(const void* base, size_t el) { v = *reinterpret_cast<const u32x2*>((const uint16_t*)base + el); }
-  __device__ __forceinline__ f32x4 get() const {
-    f32x4 r;
-    r[0] = __uint_as_float(v[0] << 16); r[1] = __uint_as_float(v[0] & 0xffff0000u);
-    r[2] = __uint_as_float(v[1] << 16); r[3] = __uint_as_float(v[1] & 0xffff0000u);
-    return r;
-  }
-};
-
-// 8 channels as the packed fp16 A fragment of one 32x32x16 k-step
-template <int DT> struct Raw8;
-template <> struct Raw8<DAD_STORE_F32> {
-  f32x4 a, b;
-  __device__ __forceinline__ void load(const void* base, size_t el) {
-    const f32x4* p = reinterpret_cast<const f32x4*>((const float*)base + el);
-    a = p[0]; b = p[1];
-  }
-  __device__ __forceinline__ u32x4 frag() const {
-    return u32x4{dad_pack2<true>(a[0], a[1]), dad_pack2<true>(a[2], a[3]), dad_pack2<true>(b[0], b[1]),
-                 dad_pack2<true>(b[2], b[3])};
-  }
-};
-template <> struct Raw8<DAD_STORE_F16> {   // already fp16: widening then rounding back is the identity
-  u32x4 v;
-  __device__ __forceinline__ void load(const void* base, size_t el) { v = *reinterpret_cast<const u32x4*>((const uint16_t*)base + el); }
-  __device__ __forceinline__ u32x4 frag() const { return v; }
-};
-template <> struct Raw8<DAD_STORE_BF16> {
-  u32x4 v;
-  __device__ __forceinline__ void load(const void* base, size_t el) { v = *reinterpret_cast<const u32x4*>((const uint16_t*)base + el); }
-  __device__ __forceinline__ u32x4 frag() const {
-    u32x4 r;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      r[k] = dad_pack2<true>(__uint_as_float(v[k] << 16), __uint_as_float(v[k] & 0xffff0000u));
-    return r;
-  }
-};
-
-// utterance of slab `job`: the largest u in [0, n) with slab_off[u] <= job (empty utterances own no slab)
-__device__ __forceinline__ int slab_owner(const int32_t* slab_off, int n, int job) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (slab_off[mid] <= job) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// bias + ReLU + sum over the slab's valid rows (the part_sum half of dad_encode_f32's epilogue)
-__device__ __forceinline__ void eval_epilogue(const f32x16* acc, const float* bias, float* part, uint32_t vbits) {
-  const int lane = threadIdx.x & 63;
-  const int j = lane & 31, kh = lane >> 5;
-  float bhs[DAD_HT];
-#pragma unroll
-  for (int ht = 0; ht < DAD_HT; ++ht) bhs[ht] = bias[ht * 32 + j];
-#pragma unroll
-  for (int ht = 0; ht < DAD_HT; ++ht) {
-    float s = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const bool v = (vbits >> dad_acc_row(r, kh)) & 1u;
-      const float pre = acc[ht][r] + bhs[ht];
-      s += (v && !(pre <= 0.0f)) ? pre : 0.0f;   // ReLU that keeps a NaN (torch's), so bad features show
-    }
-    s += __shfl_xor(s, 32, 64);
-    if (kh == 0) part[ht * 32 + j] = s;
-  }
-}
-
-// FP32: k-step (d0, e, kh) uses channel d0 + 4 kh + e of both operands; the next step's x chunk and
-// W1 fragments are loaded while this step's MFMAs run (dad_encode_f32's pipeline).
-template <int DT, bool TEACH>
-__device__ __forceinline__ void eval_slab_f32(const void* store, size_t xel, const float* Ws, const float* Wt,
-                                              f32x16 (&acc0)[DAD_HT], f32x16 (&acc1)[DAD_HT]) {
-  constexpr int NW = TEACH ? 2 : 1;
-  Raw4<DT> xc, xn;
-  f32x4 wc[NW][DAD_HT], wn[NW][DAD_HT];
-  xc.load(store, xel);
-#pragma unroll
-  for (int ht = 0; ht < DAD_HT; ++ht) {
-    wc[0][ht] = *reinterpret_cast<const f32x4*>(Ws + (size_t)ht * 32 * DAD_D);
-    if constexpr (TEACH) wc[1][ht] = *reinterpret_cast<const f32x4*>(Wt + (size_t)ht * 32 * DAD_D);
-  }
-  for (int d0 = 0; d0 < DAD_D; d0 += 8) {
-    const int dn = d0 + 8 < DAD_D ? d0 + 8 : d0;   // the last step reloads itself
-    xn.load(store, xel + dn);
-#pragma unroll
-    for (int ht = 0; ht < DAD_HT; ++ht) {
-      wn[0][ht] = *reinterpret_cast<const f32x4*>(Ws + (size_t)ht * 32 * DAD_D + dn);
-      if constexpr (TEACH) wn[1][ht] = *reinterpret_cast<const f32x4*>(Wt + (size_t)ht * 32 * DAD_D + dn);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const f32x4 x = xc.get();
-#pragma unroll
-    for (int ht = 0; ht < DAD_HT; ++ht)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc0[ht] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[e], wc[0][ht][e], acc0[ht], 0, 0, 0);
-        if constexpr (TEACH) acc1[ht] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[e], wc[1][ht][e], acc1[ht], 0, 0, 0);
-      }
-    xc = xn;
-#pragma unroll
-    for (int k = 0; k < NW; ++k)
-#pragma unroll
-      for (int ht = 0; ht < DAD_HT; ++ht) wc[k][ht] = wn[k][ht];
-  }
-}
-
-// FP16: 32x32x16 k-steps; lane (i, kh) holds A[row i][k = 8 kh + j] and B[k = 8 kh + j][h = i]
-template <int DT, bool TEACH>
-__device__ __forceinline__ void eval_slab_f16(const void* store, size_t xel, const uint16_t* Ws, const uint16_t* Wt,
-                                              f32x16 (&acc0)[DAD_HT], f32x16 (&acc1)[DAD_HT]) {
-  constexpr int NW = TEACH ? 2 : 1;
-  Raw8<DT> xc, xn;
-  u32x4 wc[NW][DAD_HT], wn[NW][DAD_HT];
-  xc.load(store, xel);
-#pragma unroll
-  for (int ht = 0; ht < DAD_HT; ++ht) {
-    wc[0][ht] = *reinterpret_cast<const u32x4*>(Ws + (size_t)ht * 32 * DAD_D);
-    if constexpr (TEACH) wc[1][ht] = *reinterpret_cast<const u32x4*>(Wt + (size_t)ht * 32 * DAD_D);
-  }
-  for (int d0 = 0; d0 < DAD_D; d0 += 16) {
-    const int dn = d0 + 16 < DAD_D ? d0 + 16 : d0;
-    xn.load(store, xel + dn);
-#pragma unroll
-    for (int ht = 0; ht < DAD_HT; ++ht) {
-      wn[0][ht] = *reinterpret_cast<const u32x4*>(Ws + (size_t)ht * 32 * DAD_D + dn);
-      if constexpr (TEACH) wn[1][ht] = *reinterpret_cast<const u32x4*>(Wt + (size_t)ht * 32 * DAD_D + dn);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const f16x8 x = __builtin_bit_cast(f16x8, xc.frag());
-#pragma unroll
-    for (int ht = 0; ht < DAD_HT; ++ht) {
-      acc0[ht] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, __builtin_bit_cast(f16x8, wc[0][ht]), acc0[ht], 0, 0, 0);
-      if constexpr (TEACH)
-        acc1[ht] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, __builtin_bit_cast(f16x8, wc[1][ht]), acc1[ht], 0, 0, 0);
-    }
-    xc = xn;
-#pragma unroll
-    for (int k = 0; k < NW; ++k)
-#pragma unroll
-      for (int ht = 0; ht < DAD_HT; ++ht) wc[k][ht] = wn[k][ht];
-  }
-}
 
 template <int DT, bool TEACH, bool F16>
 __global__ __launch_bounds__(kEncThreads) void dad_eval_encode(EvalEncArgs a) {
@@ -274,64 +108,14 @@ __global__ __launch_bounds__(256) void dad_eval_w1h(const float* student, const 
   else wt[i] = dad_half_bits(teacher[DAD_OFF_W1 + i], true);
 }
 
-// One network's head for utterance u (dad_predict_head_kernel's arithmetic on the pooled embedding).
-// Returns the first-maximum argmax; *bad = a logit is not finite.  Lane 0 writes the outputs.
+// One network's head for utterance u: its slab partials summed in slab order, then eval_head_pooled.
 __device__ __forceinline__ int eval_head_one(const float* part, int s0, int s1, float len, const float* flat,
                                              int use_entropy, size_t u, float* emb, float* logits, float* probs,
                                              float* score_out, float* score_ws, bool* bad) {
   const int lane = threadIdx.x & 63;
   f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int c = s0; c < s1; ++c) s += *reinterpret_cast<const f32x4*>(part + (size_t)c * DAD_H + 4 * lane);
-  const float d = fmaxf(len, 1.0f);
-  f32x4 x;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) x[e] = s[e] / d;
-  if (emb) *reinterpret_cast<f32x4*>(emb + u * DAD_H + 4 * lane) = x;
-  const float* w2 = flat + DAD_OFF_W2;
-  const float* b2 = flat + DAD_OFF_B2;
-  float z[DAD_C];
-#pragma unroll
-  for (int c = 0; c < DAD_C; ++c) {
-    const f32x4 w = *reinterpret_cast<const f32x4*>(w2 + (size_t)c * DAD_H + 4 * lane);
-    float p = x[0] * w[0];
-    p = fmaf(x[1], w[1], p);
-    p = fmaf(x[2], w[2], p);
-    p = fmaf(x[3], w[3], p);
-    z[c] = dad_wave_sum(p) + b2[c];
-  }
-  float m = z[0];
-  int am = 0;
-  bool nf = !(fabsf(z[0]) <= 3.402823466e38f);
-#pragma unroll
-  for (int c = 1; c < DAD_C; ++c) {
-    if (z[c] > m) { m = z[c]; am = c; }
-    nf = nf || !(fabsf(z[c]) <= 3.402823466e38f);
-  }
-  *bad = nf;
-  float ex[DAD_C], se = 0.0f;
-#pragma unroll
-  for (int c = 0; c < DAD_C; ++c) { ex[c] = expf(z[c] - m); se += ex[c]; }
-  float p[DAD_C], pmax = 0.0f, ent = 0.0f;
-#pragma unroll
-  for (int c = 0; c < DAD_C; ++c) {
-    p[c] = ex[c] / se;
-    pmax = fmaxf(pmax, p[c]);
-    ent -= p[c] * log2f(p[c] + 1e-8f);            // I/utils.py:417
-  }
-  if (lane == 0) {
-    const float sc = use_entropy ? pmax * (1.0f - ent / 2.0f) : pmax;
-    if (logits) {
-#pragma unroll
-      for (int c = 0; c < DAD_C; ++c) logits[u * DAD_C + c] = z[c];
-    }
-    if (probs) {
-#pragma unroll
-      for (int c = 0; c < DAD_C; ++c) probs[u * DAD_C + c] = p[c];
-    }
-    if (score_out) score_out[u] = sc;
-    if (score_ws) score_ws[u] = sc;
-  }
-  return am;
+  return eval_head_pooled(s, len, flat, use_entropy, u, emb, logits, probs, score_out, score_ws, bad);
 }
 
 __global__ __launch_bounds__(64 * kHeadWaves) void dad_eval_head(EvalHeadArgs a) {

@@ -36,6 +36,12 @@ and the neighbour structure of a split's embeddings (dad_knn, dad_knn_vote, dad_
   knn, knn_accuracy, knn_store, cross_domain_knn_store, trustworthiness, neighbourhood_report
                       not in the reference: scikit-learn's NearestNeighbors(brute), KNeighborsClassifier's vote and
                       sklearn.manifold.trustworthiness
+
+and emotion over time, every sliding window or prefix of every utterance in one pass (dad_eval_windows,
+csrc/eval_windows.hip):
+
+  windows_host, window_frames, enqueue_eval_windows, evaluate_windows_store, early_decision_curve, duration_report,
+  windows             SSRLModel.predict / get_embeddings (I/model.py:225-265) on the features cropped to each window
 """
 import warnings
 
@@ -211,6 +217,7 @@ class EvalPlan:
         self.result_h = torch.zeros(_RESULT_WORDS, dtype=torch.int64).pin_memory()
         self._ws = None
         self._cm = None
+        self._win = {}
 
     @classmethod
     def of(cls, x):
@@ -237,6 +244,24 @@ class EvalPlan:
                         torch.zeros(_lib.CM_SLOTS, dtype=torch.float64, device=self.device),
                         torch.zeros(_lib.CM_SLOTS, dtype=torch.float64).pin_memory())
         return self._cm
+
+    def window_buffers(self, hop, span=1, mode="sliding"):
+        """What dad_eval_windows needs about this split for one (hop, span, mode), built at the first call and
+        reused: {'win_off' / 'piece_off' host int32 [n + 1] (windows_host), 'win_off_d' / 'piece_off_d' their
+        device copies, 'windows', 'pieces', 'result_d' / 'result_h' the DAD_EW_* block and its pinned host copy,
+        'ws' the workspace (grown on demand by enqueue_eval_windows)}."""
+        key = (int(hop), int(span), str(mode))
+        b = self._win.get(key)
+        if b is None:
+            win_off, piece_off = windows_host(self.store.sizes, hop, span, mode)
+            b = {"win_off": win_off, "piece_off": piece_off,
+                 "win_off_d": torch.from_numpy(win_off).to(self.device),
+                 "piece_off_d": torch.from_numpy(piece_off).to(self.device),
+                 "windows": int(win_off[-1]), "pieces": int(piece_off[-1]),
+                 "result_d": torch.zeros(_lib.EW_SLOTS, dtype=torch.int64, device=self.device),
+                 "result_h": torch.zeros(_lib.EW_SLOTS, dtype=torch.int64).pin_memory(), "ws": None}
+            self._win[key] = b
+        return b
 
 
 def enqueue_eval_split(model, plan, use_teacher=False, use_entropy=True, precision="fp32", outputs=()):
@@ -1206,3 +1231,219 @@ def neighbourhood_report(initial_model, trained_model, clean_split, noisy_split,
                 "noisy_to_clean_accuracy": cross["noisy_to_clean"]["accuracy"],
                 "clean_to_noisy_accuracy": cross["clean_to_noisy"]["accuracy"]}
     return neighbourhood_from_scores(scores(initial_model), scores(trained_model))
+
+
+# ------------------------------------------------------------------ emotion over time: windows of a split
+# Every path above answers once per utterance.  dad_eval_windows (csrc/eval_windows.hip) classifies every sliding
+# window, or every prefix, of every utterance in one pass over the store: a window's embedding is a partial sum
+# of the per-frame rows the split evaluator computes anyway.  A time-resolved prediction otherwise takes one
+# evaluate_store per crop of the features.  Definitions: include/dad.h, "windows of a split".
+
+_WIN_MODES = {"sliding": _lib.WIN_SLIDING, "prefix": _lib.WIN_PREFIX}
+_WIN_OUTPUTS = {"w_emb": ((256,), torch.float32), "w_logits": ((4,), torch.float32), "w_probs": ((4,), torch.float32),
+                "w_score": ((), torch.float32), "w_pred": ((), torch.int64)}
+_UTT_OUTPUTS = {"mean_probs": ((4,), torch.float32), "mean_pred": ((), torch.int64), "vote_pred": ((), torch.int64),
+                "last_pred": ((), torch.int64), "settle": ((), torch.int32), "switches": ((), torch.int32)}
+
+
+def _window_geometry(sizes, hop, span, mode):
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    hop, span = int(hop), int(span)
+    if mode not in _WIN_MODES:
+        raise ValueError("mode must be 'sliding' or 'prefix', got %r" % (mode,))
+    if hop < 1 or hop >= 2 ** 31 or span < 1 or span >= 2 ** 31:
+        raise ValueError("hop and span must be in [1, 2^31), got %d and %d" % (hop, span))
+    if mode == "prefix" and span != 1:
+        raise ValueError("prefix windows take span = 1, got %d" % span)
+    if len(sizes) and (sizes.min() < 0 or sizes.max() >= 2 ** 31):
+        raise ValueError("sample sizes must be in [0, 2^31)")
+    segs = -(-sizes // hop)
+    J = segs if mode == "prefix" else np.where(sizes == 0, 0, np.maximum(1, segs - span + 1))
+    return sizes, hop, span, J
+
+
+def windows_host(sizes, hop, span=1, mode="sliding"):
+    """The host side of dad_eval_windows' ragged layouts, a pure function of the per-sample sizes:
+    (win_off int32 [n + 1], piece_off int32 [n + 1]), the exclusive prefixes of every utterance's window count J
+    and piece count ceil(L / 32) + ceil(L / hop) - ceil(L / lcm(32, hop)) (its frames cut at every multiple of 32
+    and of hop).  Raises ValueError when either total reaches 2^31."""
+    sizes, hop, span, J = _window_geometry(sizes, hop, span, mode)
+    lcm = hop * 32 // int(np.gcd(hop, 32))
+    pieces = -(-sizes // 32) + -(-sizes // hop) - -(-sizes // lcm)
+    win_off = np.concatenate([[0], np.cumsum(J)])
+    piece_off = np.concatenate([[0], np.cumsum(pieces)])
+    if win_off[-1] >= 2 ** 31 or piece_off[-1] >= 2 ** 31:
+        raise ValueError("the split holds %d windows and %d pieces; the evaluator indexes them with 32 bits"
+                         % (win_off[-1], piece_off[-1]))
+    return win_off.astype(np.int32), piece_off.astype(np.int32)
+
+
+def window_frames(sizes, hop, span=1, mode="sliding"):
+    """(utterance, start, end) int64 of every window in the order of windows_host: window w is frames
+    [start[w], end[w]) of utterance[w]."""
+    sizes, hop, span, J = _window_geometry(sizes, hop, span, mode)
+    utt = np.repeat(np.arange(len(sizes), dtype=np.int64), J)
+    first = np.concatenate([[0], np.cumsum(J)])[:-1]
+    j = np.arange(len(utt), dtype=np.int64) - first[utt]
+    if mode == "prefix":
+        return utt, np.zeros(len(utt), np.int64), np.minimum((j + 1) * hop, sizes[utt])
+    return utt, j * hop, np.minimum((j + span) * hop, sizes[utt])
+
+
+def piece_frames(sizes, hop):
+    """(utterance, start, end) int64 of every piece in the order of windows_host's piece prefix."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    hop = int(hop)
+    utt, start, end = [], [], []
+    for i, L in enumerate(sizes):
+        cuts = np.union1d(np.arange(0, L, 32), np.arange(0, L, hop))
+        utt.append(np.full(len(cuts), i, np.int64))
+        start.append(cuts)
+        end.append(np.concatenate([cuts[1:], [L]]) if len(cuts) else cuts)
+    cat = lambda v: np.concatenate(v).astype(np.int64) if v else np.zeros(0, np.int64)
+    return cat(utt), cat(start), cat(end)
+
+
+def enqueue_eval_windows(model, plan, hop, span=1, mode="sliding", use_teacher=False, use_entropy=True,
+                         precision="fp32", outputs=()):
+    """dad_eval_windows on the current stream, enqueue only (no copy, no synchronisation; graph-capturable): the
+    DAD_EW_* block lands in plan.window_buffers(hop, span, mode)['result_d'].  One network per call, the teacher
+    with use_teacher.  Returns the {name: device tensor} of the requested outputs: per window 'w_emb', 'w_logits',
+    'w_probs', 'w_score', 'w_pred' (window order of windows_host), per utterance 'mean_probs', 'mean_pred',
+    'vote_pred', 'last_pred', 'settle', 'switches'."""
+    prec = _PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    dev = plan.device
+    if model.student_flat.device != dev:
+        raise RuntimeError("model on %s, store on %s" % (model.student_flat.device, dev))
+    b = plan.window_buffers(hop, span, mode)
+    out = {}
+    for name in outputs:
+        if name in _WIN_OUTPUTS:
+            (shape, dt), rows = _WIN_OUTPUTS[name], b["windows"]
+        elif name in _UTT_OUTPUTS:
+            (shape, dt), rows = _UTT_OUTPUTS[name], plan.n
+        else:
+            raise ValueError("unknown output %r (one of %s)" % (name, ", ".join(list(_WIN_OUTPUTS) + list(_UTT_OUTPUTS))))
+        out[name] = torch.empty((rows,) + shape, dtype=dt, device=dev)
+    fn = _lib.require("dad_eval_windows", "window inference")
+    need = int(_lib.require("dad_eval_windows_workspace_bytes", "window inference")(
+        plan.n, plan.slabs, b["windows"], b["pieces"], prec))
+    if b["ws"] is None or b["ws"].numel() < need:
+        b["ws"] = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    store = plan.store
+    a = _lib.DadWindowArgs()
+    a.store = store.feats.data_ptr()
+    a.rows, a.lens, a.slab_off = plan.rows_d.data_ptr(), plan.lens_d.data_ptr(), plan.slab_off_d.data_ptr()
+    a.labels = None if plan.labels_d is None else plan.labels_d.data_ptr()
+    a.params = (model.teacher_flat if use_teacher else model.student_flat).data_ptr()
+    a.win_off, a.piece_off = b["win_off_d"].data_ptr(), b["piece_off_d"].data_ptr()
+    a.win_off_host = b["win_off"].ctypes.data
+    for name, t in out.items():
+        setattr(a, name, t.data_ptr() or None)
+    a.result = b["result_d"].data_ptr()
+    a.n, a.slabs, a.windows, a.pieces = plan.n, plan.slabs, b["windows"], b["pieces"]
+    a.hop, a.span, a.mode = int(hop), int(span), _WIN_MODES[mode]
+    a.store_dtype = STORE_DTYPES[store.feats.dtype]
+    a.use_entropy = int(bool(use_entropy))
+    a.precision = prec
+    _lib.check(fn(a, _lib.ptr(b["ws"]), torch.cuda.current_stream(dev).cuda_stream), "dad_eval_windows")
+    return out
+
+
+def _window_block(host):
+    """The dict of evaluate_windows_store from the host copy of the DAD_EW_* block."""
+    conf = lambda s: host[s:s + 16].reshape(4, 4).copy()
+    curve = lambda s: host[s:s + _lib.EW_CURVE].copy()
+    return {
+        "confusion_mean": conf(_lib.EW_CONF_MEAN), "confusion_vote": conf(_lib.EW_CONF_VOTE),
+        "confusion_last": conf(_lib.EW_CONF_LAST), "n": int(host[_lib.EW_N]),
+        "n_labelled": int(host[_lib.EW_N_LABELLED]), "n_empty": int(host[_lib.EW_N_EMPTY]),
+        "n_windows": int(host[_lib.EW_N_WINDOWS]), "n_nonfinite": int(host[_lib.EW_N_NONFINITE]),
+        "reached": curve(_lib.EW_REACHED), "correct": curve(_lib.EW_CORRECT), "carried": curve(_lib.EW_CARRIED),
+        "settle_sum": int(host[_lib.EW_SETTLE_SUM]), "switches_sum": int(host[_lib.EW_SWITCHES_SUM]),
+        "settle_frames_sum": int(host[_lib.EW_SETTLE_FRAMES_SUM]), "block": host,
+    }
+
+
+def evaluate_windows_store(model, plan_or_store, hop, span=1, mode="sliding", use_teacher=False, use_entropy=True,
+                           precision="fp32", outputs=()):
+    """One dad_eval_windows over the whole split and one device-to-host copy of its result block.  Returns
+    {'confusion_mean', 'confusion_vote', 'confusion_last' [4,4] (row = label; labelled utterances with a window),
+    'n', 'n_labelled', 'n_empty', 'n_windows', 'n_nonfinite', 'reached', 'correct', 'carried' [64] (the curve over the
+    window index), 'settle_sum', 'switches_sum', 'settle_frames_sum', 'block', 'win_off' (host int32 [n + 1])} as
+    NumPy values, plus a device tensor per name in `outputs` (enqueue_eval_windows).  Raises DadError when any
+    window has a non-finite logit."""
+    plan = EvalPlan.of(plan_or_store)
+    out = enqueue_eval_windows(model, plan, hop, span, mode, use_teacher, use_entropy, precision, outputs)
+    b = plan.window_buffers(hop, span, mode)
+    b["result_h"].copy_(b["result_d"], non_blocking=True)
+    torch.cuda.current_stream(plan.device).synchronize()
+    res = _window_block(b["result_h"].numpy().copy())
+    if res["n_nonfinite"] > 0:
+        raise _lib.DadError("dad_eval_windows: %d of %d window(s) have a non-finite logit (fp16: an operand beyond "
+                            "+-65504; any precision: non-finite features)" % (res["n_nonfinite"], res["n_windows"]))
+    res["win_off"] = b["win_off"]
+    res.update(out)
+    return res
+
+
+def _curve_from_block(res, hop):
+    live = int(np.count_nonzero(res["reached"]))
+    k = max(live, 1)
+    base = int(res["reached"][0])                 # labelled utterances with a window
+    nonempty = res["n"] - res["n_empty"]
+    ratio = lambda a, b: np.divide(100.0 * a, b, out=np.zeros(len(a), np.float64), where=b > 0)
+    reached = res["reached"][:k]
+    return {
+        "frames": (np.arange(k, dtype=np.int64) + 1) * int(hop),
+        "reached": reached,
+        "accuracy": ratio(res["correct"][:k].astype(np.float64), reached),
+        "accuracy_carried": ratio(res["carried"][:k].astype(np.float64), np.full(k, base)),
+        "correct": res["correct"][:k], "carried": res["carried"][:k],
+        "mean_settle_frames": res["settle_frames_sum"] / nonempty if nonempty else 0.0,
+        "mean_switches": res["switches_sum"] / nonempty if nonempty else 0.0,
+        "final": metrics_from_confusion(res["confusion_last"]),
+    }
+
+
+def early_decision_curve(model, store_or_loader, hop, precision="fp32"):
+    """How much audio the model needs: PREFIX windows of `hop` frames over the split, from one dad_eval_windows.
+    Returns, over the prefixes j that some labelled utterance reaches (at most the block's 64): 'frames' =
+    (j + 1) * hop, 'reached' (labelled utterances with more than j prefixes), 'accuracy' (per cent correct at prefix
+    j among them), 'accuracy_carried' (per cent over every labelled non-empty utterance, one that has ended
+    counting with its last prefix), 'correct' / 'carried' (the counts), and 'mean_settle_frames' (the audio after
+    which the decision no longer changes), 'mean_switches', 'final' = metrics_from_confusion of the whole-utterance
+    predictions.  Where the longest utterance has at most 64 prefixes, accuracy_carried ends at final['accuracy']."""
+    model.eval()
+    res = evaluate_windows_store(model, store_or_loader, hop, 1, "prefix", precision=precision)
+    return _curve_from_block(res, hop)
+
+
+def duration_report(model, clean_split, noisy_split, hop):
+    """The accuracy-against-observed-duration comparison of the two domains: {'clean', 'noisy': early_decision_curve,
+    'frames_to_final': {'clean', 'noisy'}: the first `frames` at which the domain's accuracy_carried reaches its own
+    final accuracy (None if it does not within the curve)}.  Host arithmetic on the two result blocks."""
+    rep = {"frames_to_final": {}}
+    for name, split in (("clean", clean_split), ("noisy", noisy_split)):
+        c = early_decision_curve(model, split, hop)
+        rep[name] = c
+        right = int(np.trace(c["final"]["confusion_matrix"]))
+        hit = np.nonzero(c["carried"] >= right)[0]
+        rep["frames_to_final"][name] = int(c["frames"][hit[0]]) if len(hit) else None
+    return rep
+
+
+def windows(model, feats_list, hop, span=1, mode="sliding", use_teacher=False, precision="fp32",
+            outputs=("w_probs", "w_pred")):
+    """evaluate_windows_store for a list of [T_i, 768] feature tensors or arrays, through a temporary FeatureStore
+    on the model's device: the same dict ('win_off' locates utterance i's windows; window_frames gives their
+    frames)."""
+    from .data import FeatureStore
+    model.eval()
+    mats = [torch.as_tensor(f).detach().to("cpu", torch.float32).reshape(-1, 768) for f in feats_list]
+    if not mats:
+        raise ValueError("no utterances")
+    sizes = np.array([m.shape[0] for m in mats], dtype=np.int64)
+    offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    store = FeatureStore(torch.cat(mats), sizes, offsets, None, device=model.student_flat.device)
+    return evaluate_windows_store(model, store, hop, span, mode, use_teacher, True, precision, outputs)
