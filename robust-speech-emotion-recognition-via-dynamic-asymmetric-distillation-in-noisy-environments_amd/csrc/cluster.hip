@@ -4,11 +4,13 @@
 // and calinski_harabasz_score on the [n][256] embeddings of a split, with scikit-learn's meaning
 // (include/dad.h restates it).  Six launches, no floating-point atomics, every sum in a fixed order:
 //
-//   dad_cluster_prep   one workgroup per 64-row tile: the tile's per-class column sums in double, its class
-//                      counts and its count of labelled rows with a non-finite component
-//   dad_cluster_stats  one workgroup: class sums over the tiles in tile order -> counts, m, k, the valid
-//                      flag, the centroids (double), B, and the labelled rows' mean mu rounded to fp32
-//   dad_cluster_norms  |x_i - mu|^2 per row, as the diagonal of the pair kernel's own Gram block.
+//   dad_pair_prep      (pairwise.hip, 4 groups: the row's class) one workgroup per 64-row tile: the tile's per-class
+//                      column sums in double, its class counts and its count of labelled rows with a non-finite
+//                      component
+//   dad_cluster_stats  one workgroup: dad_pair_reduce (pairwise.h: class sums over the tiles in tile order ->
+//                      counts, m, the centroids in double, the labelled rows' mean mu rounded to fp32), then k,
+//                      the valid flag and B
+//   dad_pair_norms     (pairwise.hip) |x_i - mu|^2 per row, as the diagonal of the pair kernel's own Gram block.
 //                      Distances do not change under a shift, and post-ReLU embeddings share a large positive
 //                      mean: with every operand centred on mu the identity |a|^2 + |b|^2 - 2 a.b cancels
 //                      numbers of the size of the spread, not of the mean (|x|^2 ~ 90 against |x - mu|^2 ~ 3
@@ -34,7 +36,7 @@
 #include <cstdint>
 
 #include "dad_common.h"
-#include "pairwise.h"   // the Gram block, the tile walk, the squared distance and the chunk plan (shared with tsne.hip)
+#include "pairwise.h"   // the centring prologue, the Gram walk, the bin flush and the chunk plan (shared)
 
 namespace {
 
@@ -58,7 +60,7 @@ ClusterWs cluster_ws_layout(int64_t n) {
   w.norms = off;   off = dad_align(off + sizeof(float) * npad);
   w.part = off;    off = dad_align(off + sizeof(float) * maxc * npad * DAD_C);
   w.csum = off;    off = dad_align(off + sizeof(double) * rt * DAD_C * DAD_H);
-  w.cnt = off;     off = dad_align(off + sizeof(int32_t) * rt * 8);
+  w.cnt = off;     off = dad_align(off + sizeof(int32_t) * rt * (DAD_C + 1));
   w.cent = off;    off = dad_align(off + sizeof(double) * DAD_C * DAD_H);
   w.mean = off;    off = dad_align(off + sizeof(float) * DAD_H);
   w.hdr_i = off;   off = dad_align(off + sizeof(int32_t) * 8);
@@ -72,47 +74,7 @@ ClusterWs cluster_ws_layout(int64_t n) {
 // hdr_i slots
 constexpr int kHN0 = 0, kHM = 4, kHK = 5, kHValid = 6, kHBad = 7;
 
-__device__ __forceinline__ int class_of(long lab) { return lab >= 0 && lab < DAD_C ? (int)lab : -1; }
-
 }  // namespace
-
-__global__ __launch_bounds__(kThreads) void dad_cluster_prep(const float* __restrict__ emb,
-                                                             const int64_t* __restrict__ labels, int n,
-                                                             double* __restrict__ csum, int32_t* __restrict__ cnt) {
-  __shared__ int lab_s[kTile], bad_s[kTile];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tile = blockIdx.x, i0 = kTile * tile;
-  if (tid < kTile) lab_s[tid] = i0 + tid < n ? class_of(labels[i0 + tid]) : -1;
-  __syncthreads();
-  for (int rr = w; rr < kTile; rr += kThreads / 64) {
-    const int i = i0 + rr;           // (uniform in the wave)
-    bool bad = false;
-    if (i < n) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(emb + (size_t)i * DAD_H + 4 * lane);
-      bad = __ballot(nonfinite(v[0]) | nonfinite(v[1]) | nonfinite(v[2]) | nonfinite(v[3])) != 0ull;
-    }
-    if (lane == 0) bad_s[rr] = bad && lab_s[rr] >= 0;
-  }
-  double s[DAD_C] = {0.0, 0.0, 0.0, 0.0};
-  const int rows = n - i0 < kTile ? n - i0 : kTile;
-  for (int rr = 0; rr < rows; ++rr) {
-    const int c = lab_s[rr];
-    if (c < 0) continue;             // (an unlabelled row is not read: its NaNs stay out)
-    const double x = (double)emb[(size_t)(i0 + rr) * DAD_H + tid];
-#pragma unroll
-    for (int k = 0; k < DAD_C; ++k) s[k] += c == k ? x : 0.0;
-  }
-#pragma unroll
-  for (int k = 0; k < DAD_C; ++k) csum[((size_t)tile * DAD_C + k) * DAD_H + tid] = s[k];
-  __syncthreads();
-  if (tid < 8) {
-    int v = 0;
-    if (tid < DAD_C) for (int rr = 0; rr < kTile; ++rr) v += lab_s[rr] == tid;
-    else if (tid == 4) for (int rr = 0; rr < kTile; ++rr) v += bad_s[rr];
-    cnt[tile * 8 + tid] = v;
-  }
-}
 
 __global__ __launch_bounds__(kThreads) void dad_cluster_stats(const double* __restrict__ csum,
                                                               const int32_t* __restrict__ cnt, int rt,
@@ -121,27 +83,14 @@ __global__ __launch_bounds__(kThreads) void dad_cluster_stats(const double* __re
                                                               double* __restrict__ hdr_d) {
   __shared__ double red[kThreads];
   const int tid = threadIdx.x;
-  double s[DAD_C] = {0.0, 0.0, 0.0, 0.0};
-  int nc[DAD_C] = {0, 0, 0, 0}, bad = 0;
-  for (int t = 0; t < rt; ++t) {
-#pragma unroll
-    for (int k = 0; k < DAD_C; ++k) {
-      s[k] += csum[((size_t)t * DAD_C + k) * DAD_H + tid];
-      nc[k] += cnt[t * 8 + k];
-    }
-    bad += cnt[t * 8 + 4];
-  }
-  const int m = nc[0] + nc[1] + nc[2] + nc[3];
-  const int k = (nc[0] > 0) + (nc[1] > 0) + (nc[2] > 0) + (nc[3] > 0);
-  const double mu = m > 0 ? (((s[0] + s[1]) + s[2]) + s[3]) / (double)m : 0.0;
-  mean[tid] = (float)mu;
+  const PairStats<DAD_C> p = dad_pair_reduce<DAD_C>(csum, cnt, rt, tid, cent);
+  const int* nc = p.nc;
+  const int m = p.m, k = (nc[0] > 0) + (nc[1] > 0) + (nc[2] > 0) + (nc[3] > 0);
+  mean[tid] = p.mean;
   double b = 0.0;
 #pragma unroll
-  for (int c = 0; c < DAD_C; ++c) {
-    const double mc = nc[c] > 0 ? s[c] / (double)nc[c] : 0.0;
-    cent[c * DAD_H + tid] = mc;
-    b += nc[c] > 0 ? (double)nc[c] * ((mc - mu) * (mc - mu)) : 0.0;
-  }
+  for (int c = 0; c < DAD_C; ++c)
+    b += nc[c] > 0 ? (double)nc[c] * ((p.mc[c] - p.mu) * (p.mc[c] - p.mu)) : 0.0;
   red[tid] = b;
   __syncthreads();
   if (tid == 0) {
@@ -152,34 +101,9 @@ __global__ __launch_bounds__(kThreads) void dad_cluster_stats(const double* __re
     hdr_i[kHM] = m;
     hdr_i[kHK] = k;
     hdr_i[kHValid] = k >= 2 && k <= m - 1;
-    hdr_i[kHBad] = bad;
+    hdr_i[kHBad] = p.bad;
     hdr_d[0] = bs;
   }
-}
-
-// |x_i - mu|^2 as the diagonal of the pair kernel's own Gram block: the same operand values through the same
-// chain of 128 MFMAs, so (x_i - mu).(x_j - mu) of an exact duplicate j equals it bit for bit and their distance
-// is exactly 0.  One wave per 32 rows.
-__global__ __launch_bounds__(128) void dad_cluster_norms(const float* __restrict__ emb,
-                                                         const float* __restrict__ mean, int n,
-                                                         float* __restrict__ norms) {
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int kh = lane >> 5, l32 = lane & 31;
-  const int r0 = kTile * (int)blockIdx.x + 32 * w, ia = r0 + l32;
-  const float* ra = emb + (size_t)(ia < n ? ia : 0) * DAD_H + 4 * kh;
-  f32x16 acc = f32x16{};
-#pragma unroll 4
-  for (int q = 0; q < DAD_H / 8; ++q) {
-    const f32x4 v = ia < n ? *reinterpret_cast<const f32x4*>(ra + 8 * q) -
-                                 *reinterpret_cast<const f32x4*>(mean + 4 * kh + 8 * q)
-                           : f32x4{};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(v[e], v[e], acc, 0, 0, 0);
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-    if (l32 == dad_acc_row(r, kh)) norms[r0 + l32] = acc[r];   // (rt * 64 entries: padding rows get 0)
 }
 
 struct ClusterPairArgs {
@@ -205,9 +129,8 @@ __global__ __launch_bounds__(kThreads, 2) void dad_cluster_pair(ClusterPairArgs 
 #pragma unroll
     for (int c = 0; c < DAD_C; ++c) bins[r][c] = 0.0f;
 
-  const int t_end = (chunk + 1) * a.per < a.ct ? (chunk + 1) * a.per : a.ct;
-  dad_gram_walk(
-      a.emb, a.norms, a.mean, a.n, i0, chunk * a.per, t_end, 1, bt, nj_s, ni_s,
+  dad_gram_walk_chunk(
+      a.emb, a.norms, a.mean, a.n, i0, chunk, a.per, a.ct, bt, nj_s, ni_s,
       [&](int c, int j) { lj_s[c] = j < a.n ? class_of(a.labels[j]) : -1; },
       [&](int r, int, int jc, int, float d2) {
         const int cj = lj_s[jc];
@@ -215,26 +138,7 @@ __global__ __launch_bounds__(kThreads, 2) void dad_cluster_pair(ClusterPairArgs 
 #pragma unroll
         for (int c = 0; c < DAD_C; ++c) bins[r][c] += cj == c ? d : 0.0f;
       });
-  // the 32 columns of a lane half -> lane l32 = 0, by a fixed tree
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-#pragma unroll
-    for (int c = 0; c < DAD_C; ++c) {
-      float v = bins[r][c];
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-      bins[r][c] = v;
-    }
-  __syncthreads();        // the last tile's operand reads are done: bt becomes red[2][64][4]
-  if (g.l32 == 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int il = 32 * g.rh + dad_acc_row(r, g.kh);
-      *reinterpret_cast<f32x4*>(&bt[(g.ch * kTile + il) * DAD_C]) = f32x4{bins[r][0], bins[r][1], bins[r][2], bins[r][3]};
-    }
-  }
-  __syncthreads();
-  a.part[((size_t)chunk * a.npad + i0) * DAD_C + tid] = bt[tid] + bt[kTile * DAD_C + tid];
+  flush_bins<DAD_C>(bins, g, bt, a.part + ((size_t)chunk * a.npad + i0) * DAD_C);
 }
 
 struct ClusterRowArgs {
@@ -262,11 +166,7 @@ __global__ __launch_bounds__(kThreads) void dad_cluster_rows(ClusterRowArgs a) {
     double s = 0.0;
     if (c >= 0 && a.hdr_i[kHValid]) {
       float sum[DAD_C] = {0.0f, 0.0f, 0.0f, 0.0f};
-      for (int q = 0; q < a.chunks; ++q) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(a.part + ((size_t)q * a.npad + i) * DAD_C);
-#pragma unroll
-        for (int k = 0; k < DAD_C; ++k) sum[k] += v[k];
-      }
+      dad_chunk_sum4(sum, a.part, a.chunks, a.npad, i);
       double own = 0.0, other = 0.0;
       int nown = 0;
       bool have = false;
@@ -294,18 +194,8 @@ __global__ __launch_bounds__(kThreads) void dad_cluster_rows(ClusterRowArgs a) {
   __syncthreads();
   for (int rr = w; rr < kTile; rr += kThreads / 64) {
     const int c = lab_s[rr];         // (uniform in the wave)
-    double ws = 0.0;
-    if (c >= 0) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(a.emb + (size_t)(i0 + rr) * DAD_H + 4 * lane);
-      const double* mu = a.cent + c * DAD_H + 4 * lane;
-      double p = 0.0;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const double d = (double)v[e] - mu[e];
-        p += d * d;
-      }
-      ws = dad_wave_sum_d(p);
-    }
+    const double ws =
+        c >= 0 ? dad_row_compactness(a.emb + (size_t)(i0 + rr) * DAD_H, a.cent + c * DAD_H, lane) : 0.0;
     if (lane == 0) w_s[rr] = ws;
   }
   __syncthreads();
@@ -356,17 +246,7 @@ __global__ __launch_bounds__(64) void dad_cluster_final(const double* __restrict
 }
 
 extern "C" int dad_cluster_plan(int64_t n, int cus, int* row_tiles, int* chunks, int* tiles_per_chunk) {
-  if (!row_tiles || !chunks || !tiles_per_chunk) return DAD_E_ARG;
-  if (n < 1 || n > DAD_CM_MAX_N || cus < 1) return DAD_E_SHAPE;
-  // two workgroups of the pair kernel fit a CU (65 KB of LDS each): the most chunks whose grid is still
-  // resident at once (rounding up instead left 5,531 rows on 256 CUs a second round of 10 workgroups as
-  // long as the first of 512)
-  const int rt = (int)((n + kTile - 1) / kTile);
-  const PairPlan p = pair_plan(n, 2 * cus / rt, kMaxChunks);
-  *row_tiles = p.rt;
-  *chunks = p.chunks;
-  *tiles_per_chunk = p.per;
-  return DAD_OK;
+  return pair_plan_resident2(n, cus, DAD_CM_MAX_N, kMaxChunks, row_tiles, chunks, tiles_per_chunk);
 }
 
 extern "C" size_t dad_cluster_workspace_bytes(int64_t n) {
@@ -388,12 +268,11 @@ extern "C" int dad_cluster_metrics_chunked(const float* emb, const int64_t* labe
   double *wpart = ws_ptr<double>(ws, L.wpart), *silpart = ws_ptr<double>(ws, L.silpart);
   int32_t *cnt = ws_ptr<int32_t>(ws, L.cnt), *hdr_i = ws_ptr<int32_t>(ws, L.hdr_i);
 
-  hipLaunchKernelGGL(dad_cluster_prep, dim3(rt), dim3(kThreads), 0, stream, emb, labels, (int)n, csum, cnt);
-  DAD_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dad_cluster_stats, dim3(1), dim3(kThreads), 0, stream, csum, cnt, rt, cent, mean, hdr_i, hdr_d);
-  DAD_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dad_cluster_norms, dim3(rt), dim3(128), 0, stream, emb, mean, (int)n, norms);
-  DAD_TRY(hipGetLastError());
+  const auto stats = [&] {
+    hipLaunchKernelGGL(dad_cluster_stats, dim3(1), dim3(kThreads), 0, stream, csum, cnt, rt, cent, mean, hdr_i, hdr_d);
+  };
+  DAD_RET((pair_centre<DAD_C, false>(emb, PairClassGroup{labels}, nullptr, n, rt, csum, cnt, nullptr, mean, norms,
+                                     stream, stats)));
   ClusterPairArgs pa;
   pa.emb = emb; pa.labels = labels; pa.norms = norms; pa.mean = mean; pa.part = part;
   pa.n = (int)n; pa.npad = rt * kTile; pa.ct = rt; pa.per = pl.per;

@@ -7,11 +7,13 @@
 // for a row that takes no part (label outside [0, 4)); such rows and the padding behind row n are left out by
 // selection everywhere, never by a multiplication, so a NaN in them reaches no sum.
 //
-//   dad_dg_prep        one workgroup per 64-row tile: the tile's per-group column sums in double, its group counts
-//                      and weight sums, and its count of participating rows with a non-finite component
-//   dad_dg_stats       one workgroup: the tiles in tile order -> counts, weight sums, the centroids (double), the
-//                      participating rows' mean mu rounded to fp32, the centroid shifts and the repulsion
-//   dad_cluster_norms  (cluster.hip) |x_i - mu|^2 as the diagonal of the walk's own Gram block
+//   dad_pair_prep      (pairwise.hip, 8 groups, with weights) one workgroup per 64-row tile: the tile's per-group
+//                      column sums in double, its group counts and weight sums, and its count of participating rows
+//                      with a non-finite component
+//   dad_dg_stats       one workgroup: dad_pair_reduce (pairwise.h: the tiles in tile order -> counts, the centroids in
+//                      double, the participating rows' mean mu rounded to fp32), then the weight sums, the centroid
+//                      shifts and the repulsion
+//   dad_pair_norms     (pairwise.hip) |x_i - mu|^2 as the diagonal of the walk's own Gram block
 //   dad_dg_pass1       the first n x n walk (pairwise.h): per row, the sums of d2 over the participating columns and
 //                      over the columns of the row's own class, per column chunk
 //   dad_dg_rows1       one workgroup per row tile: adds the chunks in chunk order and the rows in row order ->
@@ -60,7 +62,7 @@ GapWs gap_ws_layout(int64_t n) {
   w.norms = off; off = dad_align(off + sizeof(float) * npad);
   w.part = off;  off = dad_align(off + sizeof(float) * maxc * npad * 4);     // pass 1 [..][2], then pass 2 [..][4]
   w.csum = off;  off = dad_align(off + sizeof(double) * rt * kG * DAD_H);
-  w.cnt = off;   off = dad_align(off + sizeof(int32_t) * rt * 16);
+  w.cnt = off;   off = dad_align(off + sizeof(int32_t) * rt * (kG + 1));
   w.wsum = off;  off = dad_align(off + sizeof(double) * rt * kG);
   w.cent = off;  off = dad_align(off + sizeof(double) * kG * DAD_H);
   w.mean = off;  off = dad_align(off + sizeof(float) * DAD_H);
@@ -80,92 +82,10 @@ constexpr int kHBad = 8, kHShift = 8, kHRep = 12;
 // 2 * class + domain of row i, -1 for a row that takes no part
 __device__ __forceinline__ int group_of(const int64_t* __restrict__ labels, const uint8_t* __restrict__ domain, int i,
                                         int n) {
-  if (i >= n) return -1;
-  const long lab = labels[i];
-  return lab >= 0 && lab < DAD_C ? 2 * (int)lab + (domain[i] != 0) : -1;
-}
-
-// the W bins of a lane's 16 rows -> part[chunk][i0 + row][W]: the 32 columns of a lane half by a fixed xor tree, the
-// two column halves through LDS (red: 2 * 64 * W floats, the walk's column tile, behind a barrier)
-template <int W>
-__device__ __forceinline__ void flush_bins(float (&bins)[16][W], const GramLane& g, float* __restrict__ red,
-                                           float* __restrict__ out) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-#pragma unroll
-    for (int c = 0; c < W; ++c) {
-      float v = bins[r][c];
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-      bins[r][c] = v;
-    }
-  __syncthreads();        // the last tile's operand reads are done
-  if (g.l32 == 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int il = 32 * g.rh + dad_acc_row(r, g.kh);
-#pragma unroll
-      for (int c = 0; c < W; ++c) red[(g.ch * kTile + il) * W + c] = bins[r][c];
-    }
-  }
-  __syncthreads();
-  const int tid = threadIdx.x;
-  if (tid < kTile * W) out[tid] = red[tid] + red[kTile * W + tid];
+  return i < n ? PairDomainGroup{labels, domain}(i) : -1;
 }
 
 }  // namespace
-
-__global__ __launch_bounds__(kThreads) void dad_dg_prep(const float* __restrict__ emb,
-                                                        const int64_t* __restrict__ labels,
-                                                        const uint8_t* __restrict__ domain,
-                                                        const float* __restrict__ weights, int n,
-                                                        double* __restrict__ csum, int32_t* __restrict__ cnt,
-                                                        double* __restrict__ wsum) {
-  __shared__ int g_s[kTile], bad_s[kTile];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tile = blockIdx.x, i0 = kTile * tile;
-  if (tid < kTile) g_s[tid] = group_of(labels, domain, i0 + tid, n);
-  __syncthreads();
-  for (int rr = w; rr < kTile; rr += kThreads / 64) {
-    const int i = i0 + rr;           // (uniform in the wave)
-    bool bad = false;
-    if (i < n) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(emb + (size_t)i * DAD_H + 4 * lane);
-      bad = __ballot(nonfinite(v[0]) | nonfinite(v[1]) | nonfinite(v[2]) | nonfinite(v[3])) != 0ull;
-    }
-    if (lane == 0) bad_s[rr] = bad && g_s[rr] >= 0;
-  }
-  double s[kG];
-#pragma unroll
-  for (int k = 0; k < kG; ++k) s[k] = 0.0;
-  const int rows = n - i0 < kTile ? n - i0 : kTile;
-  for (int rr = 0; rr < rows; ++rr) {
-    const int g = g_s[rr];
-    if (g < 0) continue;             // (a row that takes no part is not read: its NaNs stay out)
-    const double x = (double)emb[(size_t)(i0 + rr) * DAD_H + tid];
-#pragma unroll
-    for (int k = 0; k < kG; ++k) s[k] += g == k ? x : 0.0;
-  }
-#pragma unroll
-  for (int k = 0; k < kG; ++k) csum[((size_t)tile * kG + k) * DAD_H + tid] = s[k];
-  __syncthreads();
-  if (tid < kG) {
-    int v = 0;
-    double ws = 0.0;
-    for (int rr = 0; rr < rows; ++rr)
-      if (g_s[rr] == tid) {
-        v += 1;
-        ws += weights ? (double)weights[i0 + rr] : 1.0;
-      }
-    cnt[tile * 16 + tid] = v;
-    wsum[tile * kG + tid] = ws;
-  } else if (tid == kG) {
-    int v = 0;
-    for (int rr = 0; rr < kTile; ++rr) v += bad_s[rr];
-    cnt[tile * 16 + kHBad] = v;
-  }
-}
 
 __global__ __launch_bounds__(kThreads) void dad_dg_stats(const double* __restrict__ csum,
                                                          const int32_t* __restrict__ cnt,
@@ -175,29 +95,10 @@ __global__ __launch_bounds__(kThreads) void dad_dg_stats(const double* __restric
   constexpr int kRed = DAD_C + DAD_C * (DAD_C - 1) / 2;     // 4 shifts, 6 centroid pairs
   __shared__ double red[kRed][kThreads];
   const int tid = threadIdx.x;
-  double s[kG];
-  int nc[kG];
-#pragma unroll
-  for (int k = 0; k < kG; ++k) {
-    s[k] = 0.0;
-    nc[k] = 0;
-  }
-  for (int t = 0; t < rt; ++t)
-#pragma unroll
-    for (int k = 0; k < kG; ++k) {
-      s[k] += csum[((size_t)t * kG + k) * DAD_H + tid];
-      nc[k] += cnt[t * 16 + k];
-    }
-  int m = 0;
-  double tot = 0.0, mc[kG];
-#pragma unroll
-  for (int k = 0; k < kG; ++k) {
-    m += nc[k];
-    tot += s[k];
-    mc[k] = nc[k] > 0 ? s[k] / (double)nc[k] : 0.0;
-    cent[k * DAD_H + tid] = mc[k];
-  }
-  mean[tid] = (float)(m > 0 ? tot / (double)m : 0.0);
+  const PairStats<kG> st = dad_pair_reduce<kG>(csum, cnt, rt, tid, cent);
+  const double* mc = st.mc;
+  const int* nc = st.nc;
+  mean[tid] = st.mean;
   int q = DAD_C;
 #pragma unroll
   for (int c = 0; c < DAD_C; ++c) {
@@ -223,9 +124,7 @@ __global__ __launch_bounds__(kThreads) void dad_dg_stats(const double* __restric
   } else if (tid == kG) {
 #pragma unroll
     for (int k = 0; k < kG; ++k) hdr_i[k] = nc[k];
-    int bad = 0;
-    for (int t = 0; t < rt; ++t) bad += cnt[t * 16 + kHBad];
-    hdr_i[kHBad] = bad;
+    hdr_i[kHBad] = st.bad;
     // shifts; the repulsion: minus the mean distance of the noisy centroids of the classes with a noisy row
     double rep = 0.0;
     int pairs = 0, p = DAD_C;
@@ -269,9 +168,8 @@ __global__ __launch_bounds__(kThreads, 2) void dad_dg_pass1(GapPassArgs a) {
   float bins[16][2];
 #pragma unroll
   for (int r = 0; r < 16; ++r) bins[r][0] = bins[r][1] = 0.0f;
-  const int t_end = (chunk + 1) * a.per < a.ct ? (chunk + 1) * a.per : a.ct;
-  dad_gram_walk(
-      a.emb, a.norms, a.mean, a.n, i0, chunk * a.per, t_end, 1, bt, nj_s, ni_s,
+  dad_gram_walk_chunk(
+      a.emb, a.norms, a.mean, a.n, i0, chunk, a.per, a.ct, bt, nj_s, ni_s,
       [&](int c, int j) {
         const int gj = group_of(a.labels, a.domain, j, a.n);
         cj_s[c] = gj < 0 ? -1 : gj >> 1;
@@ -353,9 +251,8 @@ __global__ __launch_bounds__(kThreads, 2) void dad_dg_pass2(GapPassArgs a) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) bins[r][c] = 0.0f;
 
-  const int t_end = (chunk + 1) * a.per < a.ct ? (chunk + 1) * a.per : a.ct;
-  dad_gram_walk(
-      a.emb, a.norms, a.mean, a.n, i0, chunk * a.per, t_end, 1, bt, nj_s, ni_s,
+  dad_gram_walk_chunk(
+      a.emb, a.norms, a.mean, a.n, i0, chunk, a.per, a.ct, bt, nj_s, ni_s,
       [&](int c, int j) {
         const int gj = group_of(a.labels, a.domain, j, a.n);
         gj_s[c] = gj;
@@ -408,11 +305,7 @@ __global__ __launch_bounds__(kThreads) void dad_dg_rows2(GapRowArgs a) {
     float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     double wi = 0.0;
     if (gi >= 0) {
-      for (int q = 0; q < a.chunks; ++q) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(a.part + ((size_t)q * a.npad + i) * 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) sum[k] += v[k];
-      }
+      dad_chunk_sum4(sum, a.part, a.chunks, a.npad, i);
       wi = a.weights ? (double)a.weights[i] : 1.0;
     }
     v_s[tid][0] = (double)sum[0];
@@ -423,18 +316,9 @@ __global__ __launch_bounds__(kThreads) void dad_dg_rows2(GapRowArgs a) {
   __syncthreads();
   for (int rr = w; rr < kTile; rr += kThreads / 64) {
     const int gi = g_s[rr];          // (uniform in the wave)
-    double ws = 0.0;
-    if (gi >= 0 && (gi & 1)) {       // a noisy row: |x - its class's noisy centroid|^2
-      const f32x4 v = *reinterpret_cast<const f32x4*>(a.emb + (size_t)(i0 + rr) * DAD_H + 4 * lane);
-      const double* mu = a.cent + gi * DAD_H + 4 * lane;
-      double p = 0.0;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const double d = (double)v[e] - mu[e];
-        p += d * d;
-      }
-      ws = dad_wave_sum_d(p);
-    }
+    // a noisy row: |x - its class's noisy centroid|^2
+    const double ws = gi >= 0 && (gi & 1)
+                          ? dad_row_compactness(a.emb + (size_t)(i0 + rr) * DAD_H, a.cent + gi * DAD_H, lane) : 0.0;
     if (lane == 0) w_s[rr] = ws;
   }
   __syncthreads();
@@ -525,15 +409,7 @@ __global__ __launch_bounds__(64) void dad_dg_final(const double* __restrict__ bi
 }
 
 extern "C" int dad_domain_gap_plan(int64_t n, int cus, int* row_tiles, int* chunks, int* tiles_per_chunk) {
-  if (!row_tiles || !chunks || !tiles_per_chunk) return DAD_E_ARG;
-  if (n < 1 || n > DAD_DG_MAX_N || cus < 1) return DAD_E_SHAPE;
-  // two workgroups of a pass fit a CU (65 KB of LDS each): the most chunks whose grid is resident at once
-  const int rt = (int)((n + kTile - 1) / kTile);
-  const PairPlan p = pair_plan(n, 2 * cus / rt, kMaxChunks);
-  *row_tiles = p.rt;
-  *chunks = p.chunks;
-  *tiles_per_chunk = p.per;
-  return DAD_OK;
+  return pair_plan_resident2(n, cus, DAD_DG_MAX_N, kMaxChunks, row_tiles, chunks, tiles_per_chunk);
 }
 
 extern "C" size_t dad_domain_gap_workspace_bytes(int64_t n) {
@@ -558,13 +434,11 @@ extern "C" int dad_domain_gap_chunked(const float* emb, const int64_t* labels, c
   double* bins = ws_ptr<double>(ws, L.bins);
   int32_t *cnt = ws_ptr<int32_t>(ws, L.cnt), *hdr_i = ws_ptr<int32_t>(ws, L.hdr_i);
 
-  hipLaunchKernelGGL(dad_dg_prep, dim3(rt), dim3(kThreads), 0, stream, emb, labels, domain, weights, (int)n, csum, cnt,
-                     wsum);
-  DAD_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dad_dg_stats, dim3(1), dim3(kThreads), 0, stream, csum, cnt, wsum, rt, cent, mean, hdr_i, hdr_d);
-  DAD_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dad_cluster_norms, dim3(rt), dim3(128), 0, stream, emb, mean, (int)n, norms);
-  DAD_TRY(hipGetLastError());
+  const auto stats = [&] {
+    hipLaunchKernelGGL(dad_dg_stats, dim3(1), dim3(kThreads), 0, stream, csum, cnt, wsum, rt, cent, mean, hdr_i, hdr_d);
+  };
+  DAD_RET((pair_centre<kG, true>(emb, PairDomainGroup{labels, domain}, weights, n, rt, csum, cnt, wsum, mean, norms,
+                                 stream, stats)));
   GapPassArgs pa;
   pa.emb = emb; pa.labels = labels; pa.domain = domain; pa.weights = weights; pa.norms = norms; pa.mean = mean;
   pa.coef = coef; pa.part = part; pa.n = (int)n; pa.npad = rt * kTile; pa.ct = rt; pa.per = pl.per;

@@ -4,10 +4,12 @@
 // on bits that do not depend on the chunking, so every chunk count gives the same output bits.
 //
 //   dad_knn
-//     dad_knn_colsum     one workgroup per 64-row tile: the participating rows' column sums in double, their count
-//                        and the count of those with a non-finite component
-//     dad_knn_mean       one workgroup: the tiles in tile order -> the participating rows' mean rounded to fp32
-//     dad_cluster_norms  (cluster.hip) |x_i - mu|^2 as the diagonal of the Gram block
+//     dad_pair_prep      (pairwise.hip, one group: the rows with group >= 0) one workgroup per 64-row tile: the
+//                        participating rows' column sums in double, their count and the count of those with a
+//                        non-finite component
+//     dad_pair_mean      (pairwise.hip) one workgroup: the tiles in tile order -> the participating rows' mean
+//                        rounded to fp32, the counts into the workspace's first words
+//     dad_pair_norms     (pairwise.hip) |x_i - mu|^2 as the diagonal of the Gram block
 //     dad_knn_pair       pairwise.h's walk.  Workgroup (row tile, chunk).  The walk's epilogue puts the tile's
 //                        dad_pair_d2 into LDS -- into bt itself, behind a barrier that ends every wave's operand reads
 //                        -- and behind a second barrier four lanes per row mark the columns that are candidates below
@@ -19,7 +21,7 @@
 //                        maximum; the confusion block by integer atomics (LDS, then one global add per slot and
 //                        workgroup)
 //   dad_trustworthiness
-//     colsum, mean, norms as above over all rows
+//     prep, mean, norms as above over all rows
 //     dad_knn_y          lane = row: the k nearest rows of Y by the same key, from the fp32 differences
 //     dad_knn_gather     one wave per 32 rows: D_ij of the row's k map neighbours as the diagonal of a Gram block
 //                        whose B operand is the neighbours' rows (the same operand values through the same chain of
@@ -48,10 +50,11 @@ constexpr int kMaxChunks = DAD_KNN_MAX_CHUNKS;
 constexpr int kMaxK = DAD_KNN_MAX_K;
 constexpr int kDtLd = kTile + 1;           // row stride of the d2 tile in bt (odd: a column is conflict-free)
 constexpr uint64_t kEmpty = ~0ull;         // above every key (a key's high word is at most 0x7fffffff)
-constexpr int kHdrBad = DAD_KNN_WS_NONFINITE, kHdrM = 1;
+constexpr int kHdrBad = DAD_KNN_WS_NONFINITE;
 
 static_assert(kTile == kGramTile && kTile == 64 && DAD_H == 256, "the Gram block's wave / lane mapping");
 static_assert(kTile * kDtLd <= kTile * kGramLd, "the d2 tile fits the staged column tile");
+static_assert(kHdrBad == kPairHdrBad, "dad_pair_mean writes the non-finite count where include/dad.h promises it");
 
 struct KnnWs {
   size_t hdr, mean, norms, csum, cnt, keys, ynbr, thr, pen, bytes;
@@ -128,55 +131,6 @@ __device__ __forceinline__ bool knn_candidate(int mode, int gi, int gj) {
 
 }  // namespace
 
-__global__ __launch_bounds__(kThreads) void dad_knn_colsum(const float* __restrict__ emb,
-                                                           const int32_t* __restrict__ group, int n,
-                                                           double* __restrict__ csum, int32_t* __restrict__ cnt) {
-  __shared__ int g_s[kTile], bad_s[kTile];
-  const int tid = threadIdx.x, tile = blockIdx.x, i0 = kTile * tile;
-  if (tid < kTile) {
-    g_s[tid] = i0 + tid < n ? (group ? group[i0 + tid] : 0) : -1;
-    bad_s[tid] = 0;
-  }
-  __syncthreads();
-  const int rows = n - i0 < kTile ? n - i0 : kTile;
-  double s = 0.0;
-  for (int rr = 0; rr < rows; ++rr) {
-    if (g_s[rr] < 0) continue;       // (a row that takes no part is not read: its NaNs stay out)
-    const float x = emb[(size_t)(i0 + rr) * DAD_H + tid];
-    if (nonfinite(x)) bad_s[rr] = 1;
-    s += (double)x;
-  }
-  csum[(size_t)tile * DAD_H + tid] = s;
-  __syncthreads();
-  if (tid == 0) {
-    int m = 0, bad = 0;
-    for (int rr = 0; rr < kTile; ++rr) {
-      m += g_s[rr] >= 0;
-      bad += bad_s[rr];
-    }
-    cnt[2 * tile] = m;
-    cnt[2 * tile + 1] = bad;
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void dad_knn_mean(const double* __restrict__ csum,
-                                                         const int32_t* __restrict__ cnt, int rt,
-                                                         float* __restrict__ mean, int32_t* __restrict__ hdr) {
-  const int tid = threadIdx.x;
-  double s = 0.0;
-  int m = 0, bad = 0;
-  for (int t = 0; t < rt; ++t) {
-    s += csum[(size_t)t * DAD_H + tid];
-    m += cnt[2 * t];
-    bad += cnt[2 * t + 1];
-  }
-  mean[tid] = m > 0 ? (float)(s / (double)m) : 0.0f;
-  if (tid == 0) {
-    hdr[kHdrBad] = bad;
-    hdr[kHdrM] = m;
-  }
-}
-
 struct KnnPairArgs {
   const float* emb;
   const int32_t* group;
@@ -201,9 +155,8 @@ __global__ __launch_bounds__(kThreads, KCAP <= 16 ? 2 : 1) void dad_knn_pair(Knn
   float* dt = bt;       // the d2 tile [64][kDtLd], between the walk's operand reads and its next staging
   const int row = tid >> 2, q4 = tid & 3;        // the filter: four lanes per row, 16 columns each
 
-  const int t_end = (chunk + 1) * a.per < a.ct ? (chunk + 1) * a.per : a.ct;
-  dad_gram_walk(
-      a.emb, a.norms, a.mean, n, i0, chunk * a.per, t_end, 1, bt, nj_s, ni_s,
+  dad_gram_walk_chunk(
+      a.emb, a.norms, a.mean, n, i0, chunk, a.per, a.ct, bt, nj_s, ni_s,
       [&](int c, int j) { gj_s[c] = j < n ? (a.group ? a.group[j] : 0) : -1; },
       [&](int r, int ig, int jc, int jg, float d2) {
         if (r == 0) __syncthreads();       // every wave's operand reads of this tile are done
@@ -393,9 +346,8 @@ __global__ __launch_bounds__(kThreads, KCAP <= 16 ? 2 : 1) void dad_knn_count(Kn
   float* dt = bt;
   const int row = tid >> 2, q4 = tid & 3;        // four lanes per row, 16 columns each
 
-  const int t_end = (chunk + 1) * a.per < a.ct ? (chunk + 1) * a.per : a.ct;
-  dad_gram_walk(
-      a.emb, a.norms, a.mean, n, i0, chunk * a.per, t_end, 1, bt, nj_s, ni_s, [](int, int) {},
+  dad_gram_walk_chunk(
+      a.emb, a.norms, a.mean, n, i0, chunk, a.per, a.ct, bt, nj_s, ni_s, [](int, int) {},
       [&](int r, int ig, int jc, int jg, float d2) {
         if (r == 0) __syncthreads();       // every wave's operand reads of this tile are done
         dt[(ig - i0) * kDtLd + jc] = d2;
@@ -479,29 +431,20 @@ namespace {
 
 int knn_shape(int64_t n, int k) { return n < 1 || n > DAD_KNN_MAX_N || k < 1 || k > kMaxK ? DAD_E_SHAPE : DAD_OK; }
 
-// pair_resolve with the planner's k
-int knn_resolve(int64_t n, int k, int chunks, PairPlan* pl) {
-  if (chunks > 0) {
-    *pl = pair_plan(n, chunks, kMaxChunks);
-    return DAD_OK;
-  }
-  int cus = 0;
-  DAD_RET(device_cus(&cus));
-  return dad_knn_plan(n, k, cus, &pl->rt, &pl->chunks, &pl->per);
+// dad_knn_plan at this k, as pair_resolve's planner
+auto knn_planner(int k) {
+  return [k](int64_t n, int cus, int* rt, int* ch, int* per) { return dad_knn_plan(n, k, cus, rt, ch, per); };
 }
 
-// colsum, mean, norms: what every walk of this file starts from
+// what every walk of this file starts from: the mean of the rows with group >= 0, their norms, the header
 int knn_centre(const float* emb, const int32_t* group, int64_t n, int rt, const KnnWs& L, void* ws, hipStream_t stream) {
-  float *mean = ws_ptr<float>(ws, L.mean), *norms = ws_ptr<float>(ws, L.norms);
+  float* mean = ws_ptr<float>(ws, L.mean);
   double* csum = ws_ptr<double>(ws, L.csum);
   int32_t *cnt = ws_ptr<int32_t>(ws, L.cnt), *hdr = ws_ptr<int32_t>(ws, L.hdr);
-  hipLaunchKernelGGL(dad_knn_colsum, dim3(rt), dim3(kThreads), 0, stream, emb, group, (int)n, csum, cnt);
-  DAD_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dad_knn_mean, dim3(1), dim3(kThreads), 0, stream, csum, cnt, rt, mean, hdr);
-  DAD_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dad_cluster_norms, dim3(rt), dim3(128), 0, stream, emb, mean, (int)n, norms);
-  DAD_TRY(hipGetLastError());
-  return DAD_OK;
+  return pair_centre<1, false>(emb, PairInt32Group{group}, nullptr, n, rt, csum, cnt, nullptr, mean,
+                               ws_ptr<float>(ws, L.norms), stream, [&] {
+    hipLaunchKernelGGL(dad_pair_mean, dim3(1), dim3(kThreads), 0, stream, csum, cnt, rt, mean, hdr);
+  });
 }
 
 }  // namespace
@@ -511,11 +454,7 @@ extern "C" int dad_knn_plan(int64_t n, int k, int cus, int* row_tiles, int* chun
   if (knn_shape(n, k) || cus < 1) return DAD_E_SHAPE;
   // the most chunks whose grid is still resident at once: two workgroups a CU up to k = 16, one above (the lists' LDS)
   const int rt = (int)((n + kTile - 1) / kTile);
-  const PairPlan p = pair_plan(n, (k <= 16 ? 2 : 1) * cus / rt, kMaxChunks);
-  *row_tiles = p.rt;
-  *chunks = p.chunks;
-  *tiles_per_chunk = p.per;
-  return DAD_OK;
+  return pair_plan_out(pair_plan(n, (k <= 16 ? 2 : 1) * cus / rt, kMaxChunks), row_tiles, chunks, tiles_per_chunk);
 }
 
 extern "C" size_t dad_knn_workspace_bytes(int64_t n, int k) {
@@ -529,7 +468,7 @@ extern "C" int dad_knn_chunked(const float* emb, const int32_t* group, int64_t n
   if (mode != DAD_KNN_ALL && mode != DAD_KNN_SAME && mode != DAD_KNN_OTHER) return DAD_E_ARG;
   DAD_RET(knn_shape(n, k));
   PairPlan pl;
-  DAD_RET(knn_resolve(n, k, chunks, &pl));
+  DAD_RET(pair_resolve(n, chunks, kMaxChunks, knn_planner(k), &pl));
   hipStream_t stream = (hipStream_t)stream_;
   const KnnWs L = knn_ws_layout(n, k);
   DAD_RET(knn_centre(emb, group, n, pl.rt, L, ws, stream));
@@ -569,7 +508,7 @@ extern "C" int dad_trustworthiness_chunked(const float* emb, const float* Y, int
   DAD_RET(knn_shape(n, k));
   if (2 * (int64_t)k >= n) return DAD_E_SHAPE;     // scikit-learn: n_neighbors < n_samples / 2
   PairPlan pl;
-  DAD_RET(knn_resolve(n, k, chunks, &pl));
+  DAD_RET(pair_resolve(n, chunks, kMaxChunks, knn_planner(k), &pl));
   hipStream_t stream = (hipStream_t)stream_;
   const KnnWs L = knn_ws_layout(n, k);
   DAD_RET(knn_centre(emb, nullptr, n, pl.rt, L, ws, stream));

@@ -393,10 +393,7 @@ extern "C" int dad_scl_plan(int64_t n, int cus, int* row_tiles, int* chunks, int
   if (!row_tiles || !chunks || !tiles_per_chunk) return DAD_E_ARG;
   if (n < 1 || n > DAD_SCL_MAX_N || cus < 1) return DAD_E_SHAPE;
   const SclPlan p = scl_plan_of(n, cus);
-  *row_tiles = p.rt;
-  *chunks = p.chunks;
-  *tiles_per_chunk = p.per;
-  return DAD_OK;
+  return pair_plan_out(PairPlan{p.rt, p.chunks, p.per}, row_tiles, chunks, tiles_per_chunk);
 }
 
 extern "C" size_t dad_scl_workspace_bytes(int64_t n) {

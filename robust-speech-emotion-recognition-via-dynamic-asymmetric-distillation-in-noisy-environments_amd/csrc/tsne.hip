@@ -4,10 +4,11 @@
 // restates the arithmetic); no floating-point atomics, every sum in a fixed order:
 //
 //   dad_tsne_affinities   _joint_probabilities
-//     dad_tsne_colsum     one workgroup per 64-row tile: the tile's column sums in double, its count of rows with a
-//                         non-finite component
-//     dad_tsne_mean       one workgroup: the tiles in tile order -> the rows' mean rounded to fp32, the count
-//     dad_cluster_norms   (cluster.hip) |x_i - mu|^2 as the diagonal of the Gram block
+//     dad_pair_prep       (pairwise.hip, one group: every row) one workgroup per 64-row tile: the tile's column sums
+//                         in double, its count of rows with a non-finite component
+//     dad_pair_mean       (pairwise.hip) one workgroup: the tiles in tile order -> the rows' mean rounded to fp32, the
+//                         count into the workspace's first word
+//     dad_pair_norms      (pairwise.hip) |x_i - mu|^2 as the diagonal of the Gram block
 //     dad_tsne_dist       pairwise.h's walk of the Gram block per 64 x 64 tile -> D_ij = dad_pair_d2
 //                         into P (D_ii = 0; a duplicate row's distance is exactly 0)
 //     dad_tsne_search     one wave per row: scikit-learn's _binary_search_perplexity in double on the row's fp32
@@ -51,6 +52,7 @@ constexpr int kExplore = 250;              // TSNE._EXPLORATION_MAX_ITER
 constexpr double kEps = 2.220446049250313e-16;
 
 static_assert(kTile == kGramTile && kTile == 64 && DAD_H == 256, "the Gram block's wave / lane mapping");
+static_assert(DAD_TS_WS_NONFINITE == kPairHdrBad, "dad_pair_mean writes the count where include/dad.h promises it");
 
 struct RunHdr {
   int32_t stop, phase, best_iter, nhist;
@@ -58,7 +60,7 @@ struct RunHdr {
 };
 
 struct TsneWs {
-  size_t hdr, mean, norms, csum, bad, tsum, total, part, partd, upd, gains, bytes;
+  size_t hdr, mean, norms, csum, cnt, tsum, total, part, partd, upd, gains, bytes;
 };
 
 // (a function of n alone)
@@ -67,11 +69,11 @@ TsneWs tsne_ws_layout(int64_t n) {
   const size_t rt = (size_t)((n + kTile - 1) / kTile), npad = rt * kTile;
   const size_t maxc = rt < (size_t)kMaxChunks ? rt : (size_t)kMaxChunks;
   size_t off = 0;
-  w.hdr = off;    off = dad_align(off + 256);        // int32 [0]: DAD_TS_WS_NONFINITE; RunHdr at byte 64
+  w.hdr = off;    off = dad_align(off + 256);        // int32 [0]: DAD_TS_WS_NONFINITE, [1]: n; RunHdr at byte 64
   w.mean = off;   off = dad_align(off + sizeof(float) * DAD_H);
   w.norms = off;  off = dad_align(off + sizeof(float) * npad);
   w.csum = off;   off = dad_align(off + sizeof(double) * rt * DAD_H);
-  w.bad = off;    off = dad_align(off + sizeof(int32_t) * rt);
+  w.cnt = off;    off = dad_align(off + sizeof(int32_t) * rt * 2);
   w.tsum = off;   off = dad_align(off + sizeof(double) * rt * rt);
   w.total = off;  off = dad_align(off + sizeof(double) * 2);
   w.part = off;   off = dad_align(off + sizeof(float) * maxc * 5 * npad);
@@ -99,42 +101,6 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------- affinities
-__global__ __launch_bounds__(kThreads) void dad_tsne_colsum(const float* __restrict__ emb, int n,
-                                                            double* __restrict__ csum, int32_t* __restrict__ bad) {
-  __shared__ int bad_s[kTile];
-  const int tid = threadIdx.x, tile = blockIdx.x, i0 = kTile * tile;
-  if (tid < kTile) bad_s[tid] = 0;
-  __syncthreads();
-  const int rows = n - i0 < kTile ? n - i0 : kTile;
-  double s = 0.0;
-  for (int rr = 0; rr < rows; ++rr) {
-    const float x = emb[(size_t)(i0 + rr) * DAD_H + tid];
-    if (nonfinite(x)) bad_s[rr] = 1;
-    s += (double)x;
-  }
-  csum[(size_t)tile * DAD_H + tid] = s;
-  __syncthreads();
-  if (tid == 0) {
-    int v = 0;
-    for (int rr = 0; rr < kTile; ++rr) v += bad_s[rr];
-    bad[tile] = v;
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void dad_tsne_mean(const double* __restrict__ csum,
-                                                          const int32_t* __restrict__ bad, int rt, int n,
-                                                          float* __restrict__ mean, int32_t* __restrict__ hdr) {
-  const int tid = threadIdx.x;
-  double s = 0.0;
-  for (int t = 0; t < rt; ++t) s += csum[(size_t)t * DAD_H + tid];
-  mean[tid] = (float)(s / (double)n);
-  if (tid == 0) {
-    int v = 0;
-    for (int t = 0; t < rt; ++t) v += bad[t];
-    hdr[DAD_TS_WS_NONFINITE] = v;
-  }
-}
-
 // D_ij into P for i, j < n.  Grid (row tiles, y): workgroup (x, y) takes the column tiles y, y + gridDim.y, ...
 __global__ __launch_bounds__(kThreads, 2) void dad_tsne_dist(const float* __restrict__ emb,
                                                              const float* __restrict__ norms,
@@ -494,11 +460,7 @@ extern "C" int dad_tsne_plan(int64_t n, int cus, int* row_tiles, int* chunks, in
   // 5 n partial sums for the single workgroup of the step launch to read
   const int rt = (int)((n + kTile - 1) / kTile);
   const int want = 4 * cus / rt;
-  const PairPlan p = pair_plan(n, want < rt / 4 ? want : rt / 4, kMaxChunks);
-  *row_tiles = p.rt;
-  *chunks = p.chunks;
-  *tiles_per_chunk = p.per;
-  return DAD_OK;
+  return pair_plan_out(pair_plan(n, want < rt / 4 ? want : rt / 4, kMaxChunks), row_tiles, chunks, tiles_per_chunk);
 }
 
 extern "C" size_t dad_tsne_workspace_bytes(int64_t n) {
@@ -516,14 +478,11 @@ extern "C" int dad_tsne_affinities(const float* emb, int64_t n, double perplexit
   const int rt = (int)((n + kTile - 1) / kTile), ld = rt * kTile;
   float *mean = ws_ptr<float>(ws, L.mean), *norms = ws_ptr<float>(ws, L.norms);
   double *csum = ws_ptr<double>(ws, L.csum), *tsum = ws_ptr<double>(ws, L.tsum), *total = ws_ptr<double>(ws, L.total);
-  int32_t* bad = ws_ptr<int32_t>(ws, L.bad);
+  int32_t *cnt = ws_ptr<int32_t>(ws, L.cnt), *hdr = ws_ptr<int32_t>(ws, L.hdr);
 
-  hipLaunchKernelGGL(dad_tsne_colsum, dim3(rt), dim3(kThreads), 0, stream, emb, (int)n, csum, bad);
-  DAD_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dad_tsne_mean, dim3(1), dim3(kThreads), 0, stream, csum, bad, rt, (int)n, mean, ws_ptr<int32_t>(ws, L.hdr));
-  DAD_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dad_cluster_norms, dim3(rt), dim3(128), 0, stream, emb, mean, (int)n, norms);
-  DAD_TRY(hipGetLastError());
+  DAD_RET((pair_centre<1, false>(emb, PairEveryRow{}, nullptr, n, rt, csum, cnt, nullptr, mean, norms, stream, [&] {
+    hipLaunchKernelGGL(dad_pair_mean, dim3(1), dim3(kThreads), 0, stream, csum, cnt, rt, mean, hdr);
+  })));
   hipLaunchKernelGGL(dad_tsne_dist, dim3(rt, rt < 8 ? rt : 8), dim3(kThreads), 0, stream, emb, norms, mean, (int)n, rt, ld, P);
   DAD_TRY(hipGetLastError());
   // (the perplexity as the C float scikit-learn's search receives it)
