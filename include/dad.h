@@ -622,6 +622,103 @@ size_t dad_eval_windows_workspace_bytes(int64_t n, int64_t slabs, int64_t window
  * outside [0, 2^31) or pieces < slabs; DAD_E_UNSUPPORTED: DAD_PREC_BF16.  Nothing is launched on an error. */
 int dad_eval_windows(const dad_window_args* args, void* workspace, void* stream);
 
+/* --- noise response of a split: every noise level in one store pass (csrc/eval_noise.hip) ----
+ * The train step asks the model to hold its decision under x + std * N (DataAugmentation.weak_augment /
+ * strong_augment, I/utils.py:328-350).  dad_eval_noise evaluates a split at K noise levels of ONE draw in one
+ * pass over the store.  By definition level k's outputs are SSRLModel.get_embeddings / predict (I/model.py:
+ * 225-265) in eval mode on x_t + sigma[k] * n_t over the utterance's lens[i] frames, n_t standard normal.
+ *
+ * The encoder is frame-wise and linear before its ReLU: W1 (x_t + s n_t) + b1 = W1 x_t + s W1 n_t + b1.  The slab
+ * kernel therefore runs two GEMMs per 32-frame slab on one W1 fragment, acc0 = x W1 and acc1 = n W1, and each
+ * level is only an epilogue, relu(fma(sigma[k], acc1, acc0) + b1) summed over the slab's valid rows, and a head.
+ * The same draw serves every level (common random numbers): the levels of one call differ by sigma only.
+ *
+ * Noise.  noise == NULL: counter mode.  The normal of (utterance i, frame t, channel d) is a pure function of
+ * (seed, draw, i, t, d): dad_normal_pair on a key derived from dad_stream_key(seed, draw, DAD_RNG_EVAL_NOISE), i
+ * and t >> 22, at element (t mod 2^22) * 768 + d.  It depends on neither the slab assignment, the launch
+ * geometry, the store row nor the other utterances, and no index wraps in 32 bits at any supported size.
+ * Otherwise noise is an explicit float [32 * slabs][768]: frame t of utterance i is row 32 * slab_off[i] + t (the
+ * slab-aligned layout; rows past an utterance's length are not used).  dad_eval_noise_draws writes the counter
+ * mode's normals in that layout (zeros in the unused rows) with the same device functions, so a counter call
+ * equals, bit for bit, an explicit call fed the probe's output.
+ *
+ * Precision.  DAD_PREC_FP32: exact-f32 MFMA for both GEMMs.  DAD_PREC_FP16: the rows, the noise and W1 are each
+ * rounded to fp16 (fp32 accumulation); sigma is applied in fp32 in the epilogue in both modes.
+ * Bit identities.  fma(0, finite, a) = a, and the k order, the epilogue order and the head are dad_eval_split's:
+ * a level with sigma = 0 equals dad_eval_split's emb / logits / probs / score / pred for the same network bit for
+ * bit, in both precisions and for the three store types.  Two levels with the same sigma are equal bit for bit;
+ * two calls on the same inputs write the same bits (no floating-point atomics).
+ *
+ * Per-utterance outputs, level-major, all optional (NULL = not written):
+ *   emb [K][n][256], logits [K][n][4], probs [K][n][4], score [K][n], pred [K][n]   as dad_eval_split's
+ *   drift [K][n]       |e_k - e_0|_2, an fp32 sum in a fixed order
+ *   kl [K][n]          sum_c p_0c (log p_0c - log p_kc), 0 log 0 = 0: the per-sample term of the consistency loss
+ *                      with level 0 in the teacher's role, from the log-softmax of the two logit rows
+ *   break_level [n]    int32, the smallest k >= 1 with pred_k != pred_0, or K
+ * Level 0 is the base level those three refer to (callers put sigma[0] = 0 for a clean base; not required).
+ * A length-0 utterance (or one whose slab_off entries disagree with its length) has a zero embedding, logits = b2
+ * at every level, drift 0, kl 0 and break_level K.
+ *
+ * Result block: counts[DAD_EN_COUNTS] int64 and sums[DAD_EN_SUMS] double, fixed size for DAD_EN_MAX_LEVELS
+ * levels; the slots of unused levels are written 0. */
+#define DAD_EN_MAX_LEVELS 8
+#define DAD_EN_CONF 0           /* [8][4][4] per level: row = label, column = pred_k (labelled utterances) */
+#define DAD_EN_FLIPS 128        /* [8] utterances with pred_k != pred_0, over all n */
+#define DAD_EN_SURVIVE 136      /* [8] utterances with break_level > k */
+#define DAD_EN_N 144            /* n */
+#define DAD_EN_N_LABELLED 145   /* utterances with a label in [0, 4) */
+#define DAD_EN_N_SKIPPED 146    /* label outside [0, 4), or labels == NULL (then n) */
+#define DAD_EN_N_NONFINITE 147  /* utterances with a logit that is not finite at any level */
+#define DAD_EN_LEVELS 148       /* K */
+#define DAD_EN_COUNTS 160       /* int64 slots of the counts block (149..159 reserved, written 0) */
+/* sums[.][k]: float64 sums over all n of the float32 per-utterance values, in a fixed order (strided per-thread
+ * sums and an LDS tree, as dad_eval_split's moments) */
+#define DAD_EN_SUM_SCORE 0      /* [8] */
+#define DAD_EN_SUM_DRIFT 8      /* [8] */
+#define DAD_EN_SUM_KL 16        /* [8] */
+#define DAD_EN_SUMS 24
+/* Rows as dad_eval_args (store, rows, lens, labels, slab_off, slabs).  One network per call: params is the
+ * student's or the teacher's flat vector.  Enqueue only, no allocation, no device read on the host. */
+typedef struct dad_noise_args {
+  const void* store;            /* [frames][768], dtype store_dtype */
+  const int64_t* rows;          /* [n] store row of frame 0 */
+  const int32_t* lens;          /* [n] frames */
+  const int64_t* labels;        /* [n] or NULL */
+  const int32_t* slab_off;      /* [n + 1] exclusive prefix of ceil(lens / 32) */
+  const float* params;          /* [DAD_NPARAM] flat [W1|b1|W2|b2] */
+  const float* noise;           /* [32 * slabs][768] explicit normals, or NULL: counter mode */
+  float* emb;                   /* [K][n][256] */
+  float* logits;                /* [K][n][4] */
+  float* probs;                 /* [K][n][4] */
+  float* score;                 /* [K][n] */
+  int64_t* pred;                /* [K][n] */
+  float* drift;                 /* [K][n] */
+  float* kl;                    /* [K][n] */
+  int32_t* break_level;         /* [n] */
+  int64_t* counts;              /* [DAD_EN_COUNTS], required */
+  double* sums;                 /* [DAD_EN_SUMS], required */
+  int64_t n;                    /* utterances, >= 1 */
+  int64_t slabs;                /* slab_off[n] */
+  uint64_t seed;                /* counter mode: the stream key is dad_stream_key(seed, draw, DAD_RNG_EVAL_NOISE) */
+  uint64_t draw;
+  float sigma[DAD_EN_MAX_LEVELS]; /* [levels] host values, each finite and >= 0 */
+  int32_t levels;               /* K in [1, DAD_EN_MAX_LEVELS] */
+  int32_t store_dtype;          /* DAD_STORE_* */
+  int32_t use_entropy;          /* USE_ENTROPY_IN_SCORE */
+  int32_t precision;            /* DAD_PREC_FP32 or DAD_PREC_FP16 */
+} dad_noise_args;
+/* workspace bytes of dad_eval_noise: slabs * levels * 1 KB of slab partials plus per-utterance words (0 for
+ * unsupported sizes); no initialisation needed */
+size_t dad_eval_noise_workspace_bytes(int64_t n, int64_t slabs, int levels, int precision);
+/* Checked on the host before anything is launched.  DAD_E_ARG: a required pointer is NULL, levels outside [1, 8],
+ * a sigma negative or not finite, an unknown dtype / precision; DAD_E_SHAPE: n < 1, slabs outside [0, n * 2^26],
+ * or slabs * levels * 256 >= 2^31; DAD_E_UNSUPPORTED: DAD_PREC_BF16. */
+int dad_eval_noise(const dad_noise_args* args, void* workspace, void* stream);
+/* The probe: the counter mode's normals of (args->seed, args->draw) for args->lens / slab_off / n / slabs, as the
+ * explicit layout out [32 * slabs][768] (device).  Reads no other field.  DAD_E_ARG: args, out, lens or slab_off
+ * NULL; DAD_E_SHAPE as above (levels taken as 1). */
+int dad_eval_noise_draws(const dad_noise_args* args, float* out, void* stream);
+
 /* --- class separation of a split's embeddings (csrc/cluster.hip) -------------------------
  * calculate_cluster_metrics (I/iemocap_plot_tsne.py:390-398): scikit-learn's silhouette_score and
  * calinski_harabasz_score of emb [n][256] (dad_eval_split's emb / t_emb) under labels [n], whose

@@ -25,6 +25,8 @@ from .evaluate import (cross_domain_knn_store, knn, knn_accuracy, knn_store, nei
                        trustworthiness)
 from .evaluate import (duration_report, early_decision_curve, enqueue_eval_windows, evaluate_windows_store,
                        window_frames, windows, windows_host)
+from .evaluate import (enqueue_eval_noise, evaluate_noise_store, noise_draws, noise_response_curve,
+                       robustness_report)
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
            "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "SupervisedContrastiveLoss", "TrainingTrace",
@@ -34,6 +36,7 @@ __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "D
            "knn", "knn_accuracy", "knn_store", "cross_domain_knn_store", "trustworthiness", "neighbourhood_report",
            "windows", "windows_host", "window_frames", "enqueue_eval_windows", "evaluate_windows_store",
            "early_decision_curve", "duration_report",
+           "noise_draws", "enqueue_eval_noise", "evaluate_noise_store", "noise_response_curve", "robustness_report",
            "build", "lib"]
 
 

@@ -80,6 +80,12 @@ EW_N, EW_N_LABELLED, EW_N_EMPTY, EW_N_WINDOWS, EW_N_NONFINITE = 48, 49, 50, 51, 
 EW_SETTLE_SUM, EW_SWITCHES_SUM, EW_SETTLE_FRAMES_SUM = 53, 54, 55
 EW_CURVE, EW_REACHED, EW_CORRECT, EW_CARRIED, EW_SLOTS = 64, 64, 128, 192, 256
 
+# dad_eval_noise (dad.h DAD_EN_*): the level limit, the int64 slots of the counts block, the float64 slots of the sums
+EN_MAX_LEVELS = 8
+EN_CONF, EN_FLIPS, EN_SURVIVE = 0, 128, 136
+EN_N, EN_N_LABELLED, EN_N_SKIPPED, EN_N_NONFINITE, EN_LEVELS, EN_COUNTS = 144, 145, 146, 147, 148, 160
+EN_SUM_SCORE, EN_SUM_DRIFT, EN_SUM_KL, EN_SUMS = 0, 8, 16, 24
+
 
 class DadConfig(ctypes.Structure):
     _fields_ = [
@@ -164,6 +170,15 @@ class DadWindowArgs(ctypes.Structure):
                 + [(n, ctypes.c_int32) for n in ("hop", "span", "mode", "store_dtype", "use_entropy", "precision")])
 
 
+class DadNoiseArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_void_p) for n in
+                 ("store", "rows", "lens", "labels", "slab_off", "params", "noise", "emb", "logits", "probs", "score",
+                  "pred", "drift", "kl", "break_level", "counts", "sums")]
+                + [("n", ctypes.c_int64), ("slabs", ctypes.c_int64), ("seed", ctypes.c_uint64), ("draw", ctypes.c_uint64),
+                   ("sigma", ctypes.c_float * EN_MAX_LEVELS)]
+                + [(n, ctypes.c_int32) for n in ("levels", "store_dtype", "use_entropy", "precision")])
+
+
 class DadTsneArgs(ctypes.Structure):
     _fields_ = [("max_iter", ctypes.c_int32), ("n_iter_without_progress", ctypes.c_int32),
                 ("early_exaggeration", ctypes.c_double), ("learning_rate", ctypes.c_double),
@@ -244,6 +259,9 @@ EXPORTS = {
     "dad_eval_windows_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                            ctypes.c_int64, ctypes.c_int]),
     "dad_eval_windows": (ctypes.c_int, [ctypes.POINTER(DadWindowArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_eval_noise_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "dad_eval_noise": (ctypes.c_int, [ctypes.POINTER(DadNoiseArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_eval_noise_draws": (ctypes.c_int, [ctypes.POINTER(DadNoiseArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "dad_augment": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -336,7 +354,8 @@ OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_step_plan_kernels", "dad_trace_
                     "dad_domain_gap_chunked", "dad_knn_workspace_bytes", "dad_knn_plan", "dad_knn", "dad_knn_chunked",
                     "dad_knn_vote", "dad_trustworthiness", "dad_trustworthiness_chunked",
                     "dad_scl_workspace_bytes", "dad_scl_plan", "dad_scl", "dad_scl_chunked",
-                    "dad_eval_windows_workspace_bytes", "dad_eval_windows")
+                    "dad_eval_windows_workspace_bytes", "dad_eval_windows",
+                    "dad_eval_noise_workspace_bytes", "dad_eval_noise", "dad_eval_noise_draws")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

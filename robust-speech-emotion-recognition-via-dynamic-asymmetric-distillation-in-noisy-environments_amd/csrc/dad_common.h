@@ -64,6 +64,7 @@ enum DadStream {
   DAD_RNG_TSTART = 4,    // temporal mask start         (I/utils.py:370)
   DAD_RNG_DROP1 = 5,     // classifier dropout, clean   (I/train.py:400)
   DAD_RNG_DROP2 = 6,     // classifier dropout, strong  (I/train.py:440)
+  DAD_RNG_EVAL_NOISE = 7,  // dad_eval_noise's additive noise (counter = the draw; no train-step stream)
 };
 
 __host__ __device__ __forceinline__ uint32_t dad_rng32(uint32_t i, uint32_t key) {

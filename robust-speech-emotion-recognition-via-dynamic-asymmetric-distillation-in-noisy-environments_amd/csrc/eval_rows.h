@@ -1,7 +1,8 @@
 // What the store-fed evaluators share (eval_split.hip: one embedding per utterance; eval_windows.hip: one per
-// window of an utterance): the in-place row loaders of the three store types, one slab's GEMM loop in both
-// operand precisions, the slab epilogue (bias, ReLU, masked row sum) and the head arithmetic behind a pooled
-// embedding.  Everything is internal to the including unit.
+// window of an utterance; eval_noise.hip: one per noise level of an utterance): the in-place row loaders of the
+// three store types, one slab's GEMM loop in both operand precisions (and with additive noise as a second operand),
+// the slab epilogue (bias, ReLU, masked row sum) and the head arithmetic behind a pooled embedding.  Everything is
+// internal to the including unit.
 #ifndef DAD_EVAL_ROWS_H_
 #define DAD_EVAL_ROWS_H_
 
@@ -182,10 +183,17 @@ __device__ __forceinline__ void eval_slab_f16(const void* store, size_t xel, con
 
 // One network's head behind a pooled sum (dad_predict_head_kernel's arithmetic): lane l holds the sum's
 // components 4 l .. 4 l + 3 in s; the embedding is s / max(len, 1).  Output row u.  Returns the first-maximum
-// argmax; *bad = a logit is not finite.  Lane 0 writes the outputs.
-__device__ __forceinline__ int eval_head_pooled(f32x4 s, float len, const float* flat, int use_entropy, size_t u,
-                                                float* emb, float* logits, float* probs, float* score_out,
-                                                float* score_ws, bool* bad) {
+// argmax; *bad = a logit is not finite.  Lane 0 writes the outputs.  hv receives what a caller that compares two
+// heads needs: the lane's embedding components, the logits, their maximum, sum exp(z - m) and the probabilities
+// (the same in every lane).
+struct HeadVals {
+  f32x4 x;
+  float z[DAD_C], p[DAD_C];
+  float m, se;
+};
+__device__ __forceinline__ int eval_head_pooled_v(f32x4 s, float len, const float* flat, int use_entropy, size_t u,
+                                                  float* emb, float* logits, float* probs, float* score_out,
+                                                  float* score_ws, bool* bad, HeadVals& hv) {
   const int lane = threadIdx.x & 63;
   const float d = fmaxf(len, 1.0f);
   f32x4 x;
@@ -236,7 +244,158 @@ __device__ __forceinline__ int eval_head_pooled(f32x4 s, float len, const float*
     if (score_out) score_out[u] = sc;
     if (score_ws) score_ws[u] = sc;
   }
+  hv.x = x;
+#pragma unroll
+  for (int c = 0; c < DAD_C; ++c) { hv.z[c] = z[c]; hv.p[c] = p[c]; }
+  hv.m = m; hv.se = se;
   return am;
+}
+__device__ __forceinline__ int eval_head_pooled(f32x4 s, float len, const float* flat, int use_entropy, size_t u,
+                                                float* emb, float* logits, float* probs, float* score_out,
+                                                float* score_ws, bool* bad) {
+  HeadVals hv;
+  return eval_head_pooled_v(s, len, flat, use_entropy, u, emb, logits, probs, score_out, score_ws, bad, hv);
+}
+
+// ---- additive noise on the rows (eval_noise.hip) -----------------------------------------------------------
+// The standard normal of (utterance u, frame t, channel d) under stream key skey: a pure function of those four.
+// The key is per utterance (and per block of 2^22 frames of it, so the pair index below never wraps in 32 bits:
+// 2^22 * 384 < 2^32); element (t mod 2^22) * 768 + d of that key's stream, in dad_normal_pair's pairing.
+constexpr int kNoiseFrameBits = 22;
+__device__ __forceinline__ uint32_t noise_key(uint32_t skey, int u, int t) {
+  const uint32_t ukey = dad_rng32((uint32_t)u, skey);
+  const uint32_t hi = (uint32_t)t >> kNoiseFrameBits;
+  return hi ? dad_rng32(hi, ukey) : ukey;
+}
+// pair index of channels d, d + 1 (d even) of frame t
+__device__ __forceinline__ uint32_t noise_pair(int t, int d) {
+  return ((uint32_t)t & ((1u << kNoiseFrameBits) - 1u)) * (uint32_t)(DAD_D / 2) + ((uint32_t)d >> 1);
+}
+// channels d .. d + 3 (d % 4 == 0) of the frame whose channel-0 pair is pair0
+__device__ __forceinline__ f32x4 noise_normal4(uint32_t key, uint32_t pair0, int d) {
+  f32x4 z;
+  float a, b, c, e;
+  dad_normal_pair(key, pair0 + ((uint32_t)d >> 1), a, b);
+  dad_normal_pair(key, pair0 + ((uint32_t)d >> 1) + 1u, c, e);
+  z[0] = a; z[1] = b; z[2] = c; z[3] = e;
+  return z;
+}
+
+// The noise operand of one lane's row: EXPL reads it from an explicit [rows][768] f32 array (element nel is the
+// lane's first channel), otherwise it is generated in registers (key, pair0 = noise_pair(t, lane's first channel)).
+struct NoiseSrc {
+  const float* noise; size_t nel;
+  uint32_t key, pair0;
+};
+template <bool EXPL>
+__device__ __forceinline__ f32x4 noise_load4(const NoiseSrc& n, int d) {
+  if constexpr (EXPL) return *reinterpret_cast<const f32x4*>(n.noise + n.nel + d);
+  else return noise_normal4(n.key, n.pair0, d);
+}
+// 8 channels as the packed fp16 A fragment of one 32x32x16 k-step
+template <bool EXPL>
+__device__ __forceinline__ u32x4 noise_frag8(const NoiseSrc& n, int d) {
+  const f32x4 a = noise_load4<EXPL>(n, d), b = noise_load4<EXPL>(n, d + 4);
+  return u32x4{dad_pack2<true>(a[0], a[1]), dad_pack2<true>(a[2], a[3]), dad_pack2<true>(b[0], b[1]),
+               dad_pack2<true>(b[2], b[3])};
+}
+
+// eval_slab_f32 with a second A operand on the same W fragment: acc0 += x W1, acc1 += n W1 (the k order of both
+// is eval_slab_f32's, so acc0 holds the same bits).  The next step's rows, noise and W1 are fetched while this
+// step's MFMAs run.
+template <int DT, bool EXPL>
+__device__ __forceinline__ void eval_slab_noise_f32(const void* store, size_t xel, const NoiseSrc& nz, const float* W,
+                                                    f32x16 (&acc0)[DAD_HT], f32x16 (&acc1)[DAD_HT]) {
+  Raw4<DT> xc, xn;
+  f32x4 nc, nn;
+  f32x4 wc[DAD_HT], wn[DAD_HT];
+  xc.load(store, xel);
+  nc = noise_load4<EXPL>(nz, 0);
+#pragma unroll
+  for (int ht = 0; ht < DAD_HT; ++ht) wc[ht] = *reinterpret_cast<const f32x4*>(W + (size_t)ht * 32 * DAD_D);
+  for (int d0 = 0; d0 < DAD_D; d0 += 8) {
+    const int dn = d0 + 8 < DAD_D ? d0 + 8 : d0;   // the last step reloads itself
+    xn.load(store, xel + dn);
+    nn = noise_load4<EXPL>(nz, dn);
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht) wn[ht] = *reinterpret_cast<const f32x4*>(W + (size_t)ht * 32 * DAD_D + dn);
+    __builtin_amdgcn_sched_barrier(0);
+    const f32x4 x = xc.get();
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc0[ht] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[e], wc[ht][e], acc0[ht], 0, 0, 0);
+        acc1[ht] = __builtin_amdgcn_mfma_f32_32x32x2f32(nc[e], wc[ht][e], acc1[ht], 0, 0, 0);
+      }
+    xc = xn;
+    nc = nn;
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht) wc[ht] = wn[ht];
+  }
+}
+
+// eval_slab_f16 with the noise as a second fp16 A operand (rounded to fp16 like the rows)
+template <int DT, bool EXPL>
+__device__ __forceinline__ void eval_slab_noise_f16(const void* store, size_t xel, const NoiseSrc& nz,
+                                                    const uint16_t* W, f32x16 (&acc0)[DAD_HT],
+                                                    f32x16 (&acc1)[DAD_HT]) {
+  Raw8<DT> xc, xn;
+  u32x4 nc, nn;
+  u32x4 wc[DAD_HT], wn[DAD_HT];
+  xc.load(store, xel);
+  nc = noise_frag8<EXPL>(nz, 0);
+#pragma unroll
+  for (int ht = 0; ht < DAD_HT; ++ht) wc[ht] = *reinterpret_cast<const u32x4*>(W + (size_t)ht * 32 * DAD_D);
+  for (int d0 = 0; d0 < DAD_D; d0 += 16) {
+    const int dn = d0 + 16 < DAD_D ? d0 + 16 : d0;
+    xn.load(store, xel + dn);
+    nn = noise_frag8<EXPL>(nz, dn);
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht) wn[ht] = *reinterpret_cast<const u32x4*>(W + (size_t)ht * 32 * DAD_D + dn);
+    __builtin_amdgcn_sched_barrier(0);
+    const f16x8 x = __builtin_bit_cast(f16x8, xc.frag());
+    const f16x8 z = __builtin_bit_cast(f16x8, nc);
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht) {
+      const f16x8 w = __builtin_bit_cast(f16x8, wc[ht]);
+      acc0[ht] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, w, acc0[ht], 0, 0, 0);
+      acc1[ht] = __builtin_amdgcn_mfma_f32_32x32x16_f16(z, w, acc1[ht], 0, 0, 0);
+    }
+    xc = xn;
+    nc = nn;
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht) wc[ht] = wn[ht];
+  }
+}
+
+// eval_epilogue on acc0 + sigma[k] acc1 for every level k -> part[k][256] (one fma; sigma = 0 with a finite acc1
+// leaves eval_epilogue's bits).  MAXK >= levels.  The level loop is unrolled into straight-line code behind
+// wave-uniform branches, one h tile at a time, so the accumulators are copied to VALU registers 32 at a time next
+// to their use and not all 256 ahead of a loop.
+template <int MAXK>
+__device__ __forceinline__ void eval_epilogue_noise(const f32x16* acc0, const f32x16* acc1, const float* sigma,
+                                                    int levels, const float* bias, float* part, uint32_t vbits) {
+  const int lane = threadIdx.x & 63;
+  const int j = lane & 31, kh = lane >> 5;
+#pragma unroll
+  for (int ht = 0; ht < DAD_HT; ++ht) {
+    const float bh = bias[ht * 32 + j];
+#pragma unroll
+    for (int k = 0; k < MAXK; ++k) {
+      if (k >= levels) break;
+      const float sg = sigma[k];
+      float s = 0.0f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const bool v = (vbits >> dad_acc_row(r, kh)) & 1u;
+        const float pre = fmaf(sg, acc1[ht][r], acc0[ht][r]) + bh;
+        s += (v && !(pre <= 0.0f)) ? pre : 0.0f;   // ReLU that keeps a NaN
+      }
+      s += __shfl_xor(s, 32, 64);
+      if (kh == 0) part[(size_t)k * DAD_H + ht * 32 + j] = s;
+    }
+  }
 }
 
 }  // namespace

@@ -42,6 +42,12 @@ csrc/eval_windows.hip):
 
   windows_host, window_frames, enqueue_eval_windows, evaluate_windows_store, early_decision_curve, duration_report,
   windows             SSRLModel.predict / get_embeddings (I/model.py:225-265) on the features cropped to each window
+
+and the response to additive noise, every noise level of a draw in one pass (dad_eval_noise, csrc/eval_noise.hip):
+
+  noise_draws, enqueue_eval_noise, evaluate_noise_store, noise_response_curve, robustness_report
+                      SSRLModel.predict / get_embeddings on x + sigma * N, the perturbation of
+                      DataAugmentation.weak_augment / strong_augment's noise term (I/utils.py:328-350)
 """
 import warnings
 
@@ -218,6 +224,7 @@ class EvalPlan:
         self._ws = None
         self._cm = None
         self._win = {}
+        self._noise = {}
 
     @classmethod
     def of(cls, x):
@@ -1447,3 +1454,225 @@ def windows(model, feats_list, hop, span=1, mode="sliding", use_teacher=False, p
     offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]])
     store = FeatureStore(torch.cat(mats), sizes, offsets, None, device=model.student_flat.device)
     return evaluate_windows_store(model, store, hop, span, mode, use_teacher, True, precision, outputs)
+
+
+# ------------------------------------------------------------------ noise response: every noise level in one pass
+# The train step asks the model to hold its decision under x + std * N.  dad_eval_noise (csrc/eval_noise.hip)
+# evaluates a split at K noise levels of one draw in one pass over the store: the encoder is linear before its ReLU,
+# so the pass runs one GEMM on the rows and one on the noise, and a level is an epilogue and a head.  The same draw
+# serves every level, so the levels of a call differ by sigma only.  Definitions: include/dad.h, "noise response of
+# a split".
+
+_NOISE_OUTPUTS = {"emb": ((256,), torch.float32), "logits": ((4,), torch.float32), "probs": ((4,), torch.float32),
+                  "score": ((), torch.float32), "pred": ((), torch.int64), "drift": ((), torch.float32),
+                  "kl": ((), torch.float32)}
+_NOISE_WORDS = _lib.EN_COUNTS + _lib.EN_SUMS
+
+
+def _noise_sigmas(sigmas):
+    s = [float(v) for v in np.asarray(sigmas, dtype=np.float64).reshape(-1)]
+    if not 1 <= len(s) <= _lib.EN_MAX_LEVELS:
+        raise ValueError("between 1 and %d noise levels, got %d" % (_lib.EN_MAX_LEVELS, len(s)))
+    if any(not np.isfinite(v) or v < 0 for v in s):
+        raise ValueError("noise levels must be finite and >= 0, got %r" % (s,))
+    return s
+
+
+def _noise_buffers(plan, K):
+    """The buffers of dad_eval_noise over this split at K levels, kept on the plan as the window buffers are:
+    {'result_d' / 'result_h' the DAD_EN_* block (counts, then sums) and its pinned host copy, 'ws' the workspace}."""
+    b = plan._noise.get(K)
+    if b is None:
+        b = {"result_d": torch.zeros(_NOISE_WORDS, dtype=torch.int64, device=plan.device),
+             "result_h": torch.zeros(_NOISE_WORDS, dtype=torch.int64).pin_memory(), "ws": None}
+        plan._noise[K] = b
+    return b
+
+
+def _noise_args(plan, seed, draw):
+    a = _lib.DadNoiseArgs()
+    a.rows, a.lens, a.slab_off = plan.rows_d.data_ptr(), plan.lens_d.data_ptr(), plan.slab_off_d.data_ptr()
+    a.n, a.slabs = plan.n, plan.slabs
+    a.seed, a.draw = int(seed), int(draw)
+    return a
+
+
+def noise_draws(plan, seed=0, draw=0):
+    """The probe (dad_eval_noise_draws): the standard normals that a counter-mode call with (seed, draw) adds to this
+    split, as a device tensor [32 * slabs, 768] in the explicit layout: frame t of utterance i is row
+    32 * slab_off[i] + t (zeros in the rows past an utterance's length).  Feeding it back as `noise=` repeats the
+    counter call bit for bit."""
+    plan = EvalPlan.of(plan)
+    fn = _lib.require("dad_eval_noise_draws", "the noise response")
+    out = torch.empty((32 * plan.slabs, 768), dtype=torch.float32, device=plan.device)
+    _lib.check(fn(_noise_args(plan, seed, draw), _lib.ptr(out), torch.cuda.current_stream(plan.device).cuda_stream),
+               "dad_eval_noise_draws")
+    return out
+
+
+def enqueue_eval_noise(model, plan, sigmas, seed=0, draw=0, use_teacher=False, use_entropy=True, precision="fp32",
+                       outputs=(), noise=None, _block=None):
+    """dad_eval_noise on the current stream, enqueue only (no copy, no synchronisation; graph-capturable): level k
+    evaluates x + sigmas[k] * n for one draw n of standard normals, the counter RNG's (seed, draw) or the explicit
+    device tensor `noise` [32 * slabs, 768] (noise_draws' layout).  One network per call, the teacher with
+    use_teacher.  The DAD_EN_* block lands in the plan's buffer of K = len(sigmas) levels (or in _block, an int64
+    device tensor of EN_COUNTS + EN_SUMS words).  Returns the {name: device tensor} of the requested outputs:
+    'emb', 'logits', 'probs', 'score', 'pred', 'drift', 'kl' ([K, n, ...], level-major) and 'break_level' [n]."""
+    prec = _PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    sig = _noise_sigmas(sigmas)
+    K = len(sig)
+    dev = plan.device
+    if model.student_flat.device != dev:
+        raise RuntimeError("model on %s, store on %s" % (model.student_flat.device, dev))
+    if noise is not None:
+        if (noise.dtype != torch.float32 or noise.device != dev or not noise.is_contiguous()
+                or tuple(noise.shape) != (32 * plan.slabs, 768)):
+            raise ValueError("noise must be a contiguous float32 [%d, 768] tensor on %s" % (32 * plan.slabs, dev))
+    out = {}
+    for name in outputs:
+        if name == "break_level":
+            out[name] = torch.empty((plan.n,), dtype=torch.int32, device=dev)
+        elif name in _NOISE_OUTPUTS:
+            shape, dt = _NOISE_OUTPUTS[name]
+            out[name] = torch.empty((K, plan.n) + shape, dtype=dt, device=dev)
+        else:
+            raise ValueError("unknown output %r (one of %s, break_level)" % (name, ", ".join(_NOISE_OUTPUTS)))
+    fn = _lib.require("dad_eval_noise", "the noise response")
+    b = _noise_buffers(plan, K)
+    need = int(_lib.require("dad_eval_noise_workspace_bytes", "the noise response")(plan.n, plan.slabs, K, prec))
+    if b["ws"] is None or b["ws"].numel() < need:
+        b["ws"] = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    block = b["result_d"] if _block is None else _block
+    store = plan.store
+    a = _noise_args(plan, seed, draw)
+    a.store = store.feats.data_ptr()
+    a.labels = None if plan.labels_d is None else plan.labels_d.data_ptr()
+    a.params = (model.teacher_flat if use_teacher else model.student_flat).data_ptr()
+    a.noise = None if noise is None else noise.data_ptr()
+    for name, t in out.items():
+        setattr(a, name, t.data_ptr() or None)
+    a.counts = block.data_ptr()
+    a.sums = block.data_ptr() + 8 * _lib.EN_COUNTS
+    a.levels = K
+    a.sigma[:K] = sig
+    a.store_dtype = STORE_DTYPES[store.feats.dtype]
+    a.use_entropy = int(bool(use_entropy))
+    a.precision = prec
+    _lib.check(fn(a, _lib.ptr(b["ws"]), torch.cuda.current_stream(dev).cuda_stream), "dad_eval_noise")
+    return out
+
+
+def _noise_block(host, sigmas):
+    """The dict of evaluate_noise_store from the host copy of the DAD_EN_* block."""
+    counts = host[:_lib.EN_COUNTS]
+    sums = host[_lib.EN_COUNTS:].view(np.float64)
+    K, n = int(counts[_lib.EN_LEVELS]), int(counts[_lib.EN_N])
+    res = {"n": n, "n_labelled": int(counts[_lib.EN_N_LABELLED]), "n_skipped": int(counts[_lib.EN_N_SKIPPED]),
+           "n_nonfinite": int(counts[_lib.EN_N_NONFINITE]), "n_levels": K, "sigmas": list(sigmas),
+           "confusion": counts[_lib.EN_CONF:_lib.EN_CONF + 16 * _lib.EN_MAX_LEVELS].reshape(-1, 4, 4)[:K].copy(),
+           "flips": counts[_lib.EN_FLIPS:_lib.EN_FLIPS + K].copy(),
+           "survive": counts[_lib.EN_SURVIVE:_lib.EN_SURVIVE + K].copy(),
+           "sum_score": sums[_lib.EN_SUM_SCORE:_lib.EN_SUM_SCORE + K].copy(),
+           "sum_drift": sums[_lib.EN_SUM_DRIFT:_lib.EN_SUM_DRIFT + K].copy(),
+           "sum_kl": sums[_lib.EN_SUM_KL:_lib.EN_SUM_KL + K].copy(), "block": host, "levels": []}
+    for k in range(K):
+        lv = metrics_from_confusion(res["confusion"][k]) if res["n_labelled"] else {}
+        lv.update(sigma=res["sigmas"][k], flip_rate=res["flips"][k] / n, survival=res["survive"][k] / n,
+                  mean_score=res["sum_score"][k] / n, mean_drift=res["sum_drift"][k] / n, mean_kl=res["sum_kl"][k] / n)
+        res["levels"].append(lv)
+    return res
+
+
+def _check_noise_block(res):
+    if res["n_nonfinite"] > 0:
+        raise _lib.DadError("dad_eval_noise: %d of %d utterance(s) have a non-finite logit (fp16: an operand beyond "
+                            "+-65504; any precision: non-finite features)" % (res["n_nonfinite"], res["n"]))
+
+
+def evaluate_noise_store(model, plan_or_store, sigmas, seed=0, draw=0, use_teacher=False, use_entropy=True,
+                         precision="fp32", outputs=(), noise=None):
+    """One dad_eval_noise over the whole split and one device-to-host copy of its result block.  Returns {'levels':
+    per level metrics_from_confusion's dict (when the split has labels) plus 'sigma', 'flip_rate' (predictions that
+    left level 0's), 'survival' (utterances whose break level lies above this level), 'mean_score', 'mean_drift',
+    'mean_kl'; 'confusion' [K,4,4], 'flips', 'survive' [K], 'sum_score', 'sum_drift', 'sum_kl' [K] (float64), 'n',
+    'n_labelled', 'n_skipped', 'n_nonfinite', 'n_levels', 'sigmas', 'block'} as NumPy values, plus a device tensor
+    per name in `outputs` (enqueue_eval_noise).  Raises DadError when any utterance has a non-finite logit."""
+    plan = EvalPlan.of(plan_or_store)
+    sig = _noise_sigmas(sigmas)
+    out = enqueue_eval_noise(model, plan, sig, seed, draw, use_teacher, use_entropy, precision, outputs, noise)
+    b = _noise_buffers(plan, len(sig))
+    b["result_h"].copy_(b["result_d"], non_blocking=True)
+    torch.cuda.current_stream(plan.device).synchronize()
+    res = _noise_block(b["result_h"].numpy().copy(), sig)
+    _check_noise_block(res)
+    res.update(out)
+    return res
+
+
+def default_noise_levels(cfg=None):
+    """(0.0, WEAK_NOISE_STD, STRONG_NOISE_STD) of the config (None: the IEMOCAP defaults), read at call time: the
+    perturbations training asks the model to be consistent under."""
+    from .config import ConfigView
+    view = ConfigView(flavor="iemocap") if cfg is None else cfg
+    return (0.0, float(view.WEAK_NOISE_STD), float(view.STRONG_NOISE_STD))
+
+
+_CURVE_KEYS = (("accuracy", "accuracy"), ("balanced_accuracy", "weighted_accuracy"), ("flip_rate", "flip_rate"),
+               ("mean_kl", "mean_kl"))
+
+
+def noise_response_curve(model, store_or_loader, sigmas=None, draws=8, seed=0, use_teacher=False, precision="fp32",
+                         cfg=None):
+    """The split's response to additive noise over `draws` independent draws (draw = 0 .. draws - 1 of `seed`):
+    `draws` dad_eval_noise calls enqueued into separate result blocks, one synchronisation.  sigmas=None means
+    default_noise_levels(cfg).  Returns {'sigmas', 'draws', per level lists 'accuracy', 'balanced_accuracy',
+    'flip_rate', 'mean_kl': {'mean', 'std'} (the mean and the population standard deviation across draws; per cent
+    for the two accuracies), 'per_draw' (evaluate_noise_store's dict of every draw, without outputs) and 'flip_prob'
+    [K, n], a float32 device tensor: the share of draws in which utterance i's prediction at level k left its
+    level-0 prediction}."""
+    model.eval()
+    plan = EvalPlan.of(store_or_loader)
+    sig = _noise_sigmas(default_noise_levels(cfg) if sigmas is None else sigmas)
+    draws = int(draws)
+    if draws < 1:
+        raise ValueError("draws must be >= 1")
+    if plan.labels_d is None:
+        raise ValueError("the split has no labels")
+    dev = plan.device
+    blocks_d = torch.zeros((draws, _NOISE_WORDS), dtype=torch.int64, device=dev)
+    blocks_h = torch.zeros((draws, _NOISE_WORDS), dtype=torch.int64).pin_memory()
+    flips = torch.zeros((len(sig), plan.n), dtype=torch.float32, device=dev)
+    for d in range(draws):
+        pred = enqueue_eval_noise(model, plan, sig, seed, d, use_teacher, True, precision, ("pred",),
+                                  _block=blocks_d[d])["pred"]
+        flips += (pred != pred[0:1]).to(torch.float32)
+    flips /= draws
+    blocks_h.copy_(blocks_d, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    per_draw = [_noise_block(blocks_h[d].numpy().copy(), sig) for d in range(draws)]
+    for r in per_draw:
+        _check_noise_block(r)
+    res = {"sigmas": sig, "draws": draws, "per_draw": per_draw, "flip_prob": flips}
+    for name, key in _CURVE_KEYS:
+        v = np.array([[r["levels"][k][key] for k in range(len(sig))] for r in per_draw], dtype=np.float64)
+        res[name] = {"mean": v.mean(0).tolist(), "std": v.std(0).tolist()}
+    return res
+
+
+def robustness_from_curves(initial, trained):
+    """The `initial_weights` / `trained_weights` / `improvement` block (the shape of separation_from_metrics) from two
+    noise_response_curve dicts: per level the mean accuracy (per cent) and the mean flip rate; every value a Python
+    float."""
+    pick = lambda c: {"sigmas": [float(s) for s in c["sigmas"]],
+                      "accuracy": [float(v) for v in c["accuracy"]["mean"]],
+                      "flip_rate": [float(v) for v in c["flip_rate"]["mean"]]}
+    a, b = pick(initial), pick(trained)
+    return {"initial_weights": a, "trained_weights": b,
+            "improvement": {"accuracy_change": [y - x for x, y in zip(a["accuracy"], b["accuracy"])],
+                            "flip_rate_change": [y - x for x, y in zip(a["flip_rate"], b["flip_rate"])]}}
+
+
+def robustness_report(initial_model, trained_model, store_or_loader, sigmas=None, draws=8):
+    """robustness_from_curves of noise_response_curve under the initial and the trained weights, on the same draws."""
+    return robustness_from_curves(noise_response_curve(initial_model, store_or_loader, sigmas, draws),
+                                  noise_response_curve(trained_model, store_or_loader, sigmas, draws))
