@@ -50,6 +50,24 @@ Bounds (u = 2^-24, the fp32 unit roundoff; S_x = the reference's sum with every 
   logits      |z - z_ref| <= (T + H + 8) u (|d_ref| |W2|^T + |b2|), d = the dropout-scaled embedding.
 The forward bounds hold for ALL three precisions: the 16-bit conversion is lossless on these inputs, so a 16-bit
 forward that differs from the fp32 one beyond summation order is a bug.
+
+Long problems (LONG_GEOMS, long_problem; tests/test_gpu_long_utterances.py).  GEOMS stops at T = 70; the step's pooling
+sums slab partials in batches of 16 (csrc/pool.h) and its 16-bit weight gradient takes 21 splits until the slab list
+passes 21 x 64 (csrc/dad_common.h), so utterances past 512 frames and lists past 1344 slabs run code no GEOMS entry
+reaches.  The same grid, bounds and reference serve there (sum|x||w| + |b| stays far below 1024); three things are added:
+  lengths     given per utterance, not drawn (which frame an utterance ends on is what the cases are about)
+  sentinels   The bound is a fraction of S, the magnitude sum over ALL rows: n_rows u alone is 2.7e-3 S at 16 x 1400
+              frames per side, while one slab of 1408 carries 7e-4 S.  Past about 100 slabs a dropped or doubled slab
+              therefore passes.  So channels 640 .. 767 hold values only in the frames of the weight-gradient slabs s
+              (dad_wg_total's order: clean slabs, then strong ones, padded slabs counted) with s mod 128 == channel -
+              640: xc and xn non-zero multiples of 2^-3 in +-[1/8, 2] with one sign per slab, the draws nw and ns
+              as drawn, all four 0 there in every other slab, and u = 1 there, so the feature mask keeps the channels.
+              S of a sentinel column then covers 1 slab in 128, and a lost slab lies at least 10x outside the fp16
+              bound (test_exact_problem_cpu.py asserts it for every loud slab and prints the least factor).
+  mislabel    A clean utterance the student classifies confidently has dL/de near 0, and the tail term then dominates
+              its slabs' S.  Shifting every clean label by one makes dL/de of order 1 (L3).
+L3's mask has to hold both values while the noisy utterances in which a 64-slab split begins or ends are masked in:
+its noisy utterances' noise levels and classes are given too (_L3_NOISE, _L3_LABELS).
 """
 import numpy as np
 
@@ -75,8 +93,47 @@ GEOMS = [
 ]
 
 
+SENT0, SENT_N = 640, 128       # the sentinel channels 640 .. 767 of the long problems (long_problem)
+
+
+def _ragged_lengths(seed, n, lo=700, hi=1400, pins=()):
+    """n seeded lengths in [lo, hi], each = 16 .. 31 mod 32 (so every last slab holds at least 16 frames);
+    `pins`: (utterance, smallest length) pairs, for the utterances a split boundary of L3 falls in."""
+    rs = np.random.RandomState(seed)
+    lens = 32 * rs.randint((lo + 31) // 32, hi // 32, size=n) + rs.randint(16, 32, size=n)
+    for u, least in pins:
+        while lens[u] < least:
+            lens[u] += 32
+        lens[u] = min(lens[u], hi)
+    assert lens.min() >= lo and lens.max() <= hi and np.all(lens % 32 >= 16)
+    return tuple(int(v) for v in lens)
+
+
+# L3's 64-slab splits start and end in utterances 0, 1, 2, 4, 5, 7, 8, 10, 11, 13, 14, 15 of either list (44 slabs
+# per utterance): these lengths keep the boundary slabs live, and utterance 15 has every frame.
+_L3_PINS = ((2, 1304), (5, 1176), (8, 1048), (11, 920), (14, 792), (15, 1400))
+# ... and those twelve noisy utterances must be masked in for their strong slabs to carry a gradient, while the mask
+# is to hold both values: noisy utterances 3, 6, 9 and 12 are loud (noise level 2.5) members of class 2, whose seeded
+# threshold (0.90) none of them reaches; the twelve are quiet (0.5) members of the classes 0, 1 and 3.
+_L3_OUT = (3, 6, 9, 12)
+_L3_NOISE = tuple(2.5 if u in _L3_OUT else 0.5 for u in range(16))
+_L3_LABELS = (0, 1, 3, 2, 0, 1, 2, 3, 0, 2, 1, 3, 2, 0, 1, 3)
+# The long problems (explicit lengths; module docstring "Long problems").
+LONG_GEOMS = [
+    dict(id="L1", B=2, T=544, Bn=3, Tn=577, lens_c=(544, 200), lens_n=(577, 512, 31), sentinel=True, tau="open"),
+    dict(id="L2", B=2, T=1056, Bn=2, Tn=1025, lens_c=(1056, 513), lens_n=(1025, 1000), sentinel=True, tau="open"),
+    dict(id="L3", B=16, T=1400, Bn=16, Tn=1400, lens_c=_ragged_lengths(41, 16, pins=_L3_PINS),
+         lens_n=_ragged_lengths(42, 16, pins=_L3_PINS), sentinel=True, mislabel=True, noise_n=_L3_NOISE,
+         labels_n=_L3_LABELS),
+    dict(id="S1", B=32, T=32, Bn=32, Tn=32, lens_c=tuple(int(v) for v in np.random.RandomState(43).permutation(32) + 1),
+         lens_n=tuple(int(v) for v in np.random.RandomState(44).permutation(32) + 1)),
+]
+LONG = {g["id"]: g for g in LONG_GEOMS}
+S1_PLUS = dict(LONG["S1"], id="S1plus", B=33, lens_c=LONG["S1"]["lens_c"] + (17,))
+
+
 def geom_id(g):
-    return "B%dT%d_Bn%dTn%d" % (g["B"], g["T"], g["Bn"], g["Tn"])
+    return g["id"] if "id" in g else "B%dT%d_Bn%dTn%d" % (g["B"], g["T"], g["Bn"], g["Tn"])
 
 
 def q(a, step):
@@ -100,6 +157,80 @@ def problem(B, T, Bn=None, Tn=None, seed=SEED, ragged=True):
     dr["nw"] = np.clip(np.round(dr["nw"]), -3, 3).astype(np.float32)
     dr["ns"] = np.clip(np.round(2.0 * dr["ns"]), -6, 6).astype(np.float32)
     return dict(xc=q(xc, 2.0 ** -3), mc=mc, yc=yc, xn=q(xn, 2.0 ** -3), mn=mn, yn=yn, **dr)
+
+
+def _batch_of(P, seed, lens, T, noisy, label_shift, noise=None, classes=None):
+    """synth.make_batch with the lengths given, not drawn: features on the 2^-3 grid with |x| < 17, pads 0.
+    `noise`, `classes`: the noisy utterances' noise levels and classes, where given (make_batch draws the levels
+    from U(0.5, 2.5) and shuffles the classes; the draws are made either way, so the stream stays the same)."""
+    rs = np.random.RandomState(seed)
+    B = len(lens)
+    labels = (np.arange(B) + label_shift) % P.shape[0]
+    rs.shuffle(labels)
+    if classes is not None:
+        labels = np.asarray(classes, np.int64)
+    level = rs.uniform(0.5, 2.5, size=(B, 1, 1))
+    if noise is not None:
+        level = np.asarray(noise, np.float64).reshape(B, 1, 1)
+    sigma = 0.5 + (10.0 ** (-5.0 / 20.0) * level if noisy else 0.0)
+    x = P[labels][:, None, :] + (sigma * rs.standard_normal(size=(B, T, P.shape[1]))).astype(np.float32)
+    x = np.clip(q(x, 2.0 ** -3), -16.875, 16.875)
+    pad = np.arange(T)[None, :] >= np.asarray(lens)[:, None]
+    x[pad] = 0.0
+    return x, pad, labels.astype(np.int64)
+
+
+def wg_slab(B, T, Bn, Tn, noisy, b, c):
+    """Weight-gradient slab number of 32-frame slab c of utterance b (csrc/dad_common.h dad_wg_total's order:
+    the clean slabs, then the strong ones; padded slabs count)."""
+    ncc, ncn = (T + 31) // 32, (Tn + 31) // 32
+    return B * ncc + b * ncn + c if noisy else b * ncc + c
+
+
+def _sentinels(a, first_slab, rs=None):
+    """Apply the sentinel rule to [B, T, D] array `a` in place: channel SENT0 + s mod SENT_N is zero outside the
+    frames of the slabs numbered s (utterance b's slab c is first_slab + b * ceil(T / 32) + c).  With `rs`,
+    the slab's own channel is redrawn as non-zero multiples of 2^-3 in +-[1/8, 2], one sign per slab; without,
+    it is kept."""
+    B, T, _ = a.shape
+    nc = (T + 31) // 32
+    own = SENT0 + (first_slab + np.arange(B)[:, None] * nc + np.arange(T)[None, :] // 32) % SENT_N      # [B, T]
+    bi, ti = np.arange(B)[:, None], np.arange(T)[None, :]
+    if rs is None:
+        keep = a[bi, ti, own]
+    else:
+        sign = np.repeat(rs.choice([-1.0, 1.0], size=(B, nc)), 32, axis=1)[:, :T]      # (one per slab: no cancelling)
+        keep = (rs.randint(1, 17, size=(B, T)) * sign * 2.0 ** -3).astype(a.dtype)
+    a[:, :, SENT0:SENT0 + SENT_N] = 0
+    a[bi, ti, own] = keep
+
+
+def long_problem(B, T, Bn, Tn, lens_c, lens_n, seed=SEED, sentinel=False, mislabel=False, noise_n=None, labels_n=None):
+    """problem() with explicit lengths per utterance (one of them the padded length), and optionally
+      sentinel   channels 640 .. 767 hold values only in the frames of the weight-gradient slabs s with
+                 s mod 128 == channel - 640 (xc, xn: non-zero multiples of 2^-3 in +-[1/8, 2]; nw, ns: their
+                 draws); xc, xn, nw and ns are 0 there in every other slab, and u = 1 keeps the channels
+      mislabel   every clean label shifted by one, so that dL/de of the clean rows is of order 1"""
+    assert len(lens_c) == B and max(lens_c) == T and len(lens_n) == Bn and max(lens_n) == Tn and min(lens_c + lens_n) >= 1
+    P = synth.init_weights(seed)[4]
+    xc, mc, yc = _batch_of(P, seed * 11 + 1, lens_c, T, False, 0)
+    xn, mn, yn = _batch_of(P, seed * 11 + 2, lens_n, Tn, True, 1, noise_n, labels_n)
+    dr = synth.make_draws(seed * 11 + 3, Bn, Tn)
+    dr["keep1"] = synth.make_draws(seed * 11 + 4, B, 1)["keep1"]
+    dr["nw"] = np.clip(np.round(dr["nw"]), -3, 3).astype(np.float32)
+    dr["ns"] = np.clip(np.round(2.0 * dr["ns"]), -6, 6).astype(np.float32)
+    if sentinel:
+        rs = np.random.RandomState(seed * 11 + 5)
+        _sentinels(xc, 0, rs)
+        _sentinels(xn, wg_slab(B, T, Bn, Tn, True, 0, 0), rs)
+        xc[mc] = 0.0
+        xn[mn] = 0.0
+        for k in ("nw", "ns"):
+            _sentinels(dr[k], wg_slab(B, T, Bn, Tn, True, 0, 0))
+        dr["u"][SENT0:SENT0 + SENT_N] = 1.0
+    if mislabel:
+        yc = (yc + 1) % synth.N_CLS
+    return dict(xc=xc, mc=mc, yc=yc, xn=xn, mn=mn, yn=yn, **dr)
 
 
 def tau_range(Bn):
@@ -246,15 +377,21 @@ def reference(inp, st, c, epoch):
 _CASES = {}
 
 
-def case(geom, epoch):
-    """(inputs, state, reference) of one geometry (a GEOMS entry) at `epoch`: computed once, never changed."""
-    key = (geom_id(geom), epoch)
+def case(geom, epoch, **cfg_over):
+    """(inputs, state, reference) of one geometry (a GEOMS or LONG_GEOMS entry, or S1_PLUS) at `epoch`: computed
+    once, never changed.  `cfg_over`: settings that differ from cfg() (the step under test must get them too)."""
+    key = (geom_id(geom), epoch) + tuple(sorted(cfg_over.items()))
     if key not in _CASES:
         g = dict(geom)
-        ragged = g.pop("ragged", True)
-        inp = problem(ragged=ragged, **g)
-        st = state(tau_range=tau_range(g["Bn"]))
-        _CASES[key] = (inp, st, reference(inp, st, cfg(), epoch))
+        if "id" in g:
+            del g["id"]
+            st = state(tau_range=TAU_RANGE_OPEN if g.pop("tau", None) == "open" else TAU_RANGE)
+            inp = long_problem(**g)
+        else:
+            ragged = g.pop("ragged", True)
+            inp = problem(ragged=ragged, **g)
+            st = state(tau_range=tau_range(g["Bn"]))
+        _CASES[key] = (inp, st, reference(inp, st, dict(cfg(), **cfg_over), epoch))
     return _CASES[key]
 
 

@@ -2,7 +2,11 @@
 the operands of tests/exact_problem.py are exact in fp16 and bf16, the pre-activations are exact in fp32 in any
 summation order and never 0, the DACP / ECDA gates are open with the mask decisions far from their thresholds, the
 strong branch is visible in the weight gradient, the fp32 references and a simulated 16-bit rounding of the
-weight gradient's scales lie inside the derived bound, and wrong weight gradients lie at least 10x outside it."""
+weight gradient's scales lie inside the derived bound, and wrong weight gradients lie at least 10x outside it.
+The long problems (exact_problem.LONG_GEOMS, tests/test_gpu_long_utterances.py) meet the same conditions; their own
+controls: every loud slab dropped or counted twice lies 10x outside the fp16 bound through its sentinel column, L3's 22
+splits begin and end in loud slabs, and what csrc/pool.h's loops could get wrong past 16 slabs or 512 frames lies 10x
+outside the embedding and db1 bounds."""
 import numpy as np
 import pytest
 import torch
@@ -12,6 +16,10 @@ from oracle import dad_oracle
 from oracle.torch_cpu import TorchCPUStep
 
 GEOMS = pytest.mark.parametrize("geom", X.GEOMS, ids=X.geom_id)
+# the conditions every problem must meet: the edge geometries and the long ones (tests/test_gpu_long_utterances.py)
+ALL = pytest.mark.parametrize("geom", X.GEOMS + X.LONG_GEOMS + [X.S1_PLUS], ids=X.geom_id)
+SENTINEL = pytest.mark.parametrize("geom", [g for g in X.LONG_GEOMS if g.get("sentinel")], ids=X.geom_id)
+POOLED = pytest.mark.parametrize("geom", [X.LONG["L1"], X.LONG["L2"]], ids=X.geom_id)
 EPOCH = 60
 
 
@@ -24,7 +32,7 @@ def _encoder_operands(geom):
             ("strong", xs, st["student"][0], st["student"][1])]
 
 
-@GEOMS
+@ALL
 def test_operands_survive_fp16_and_bf16(geom):
     inp = X.case(geom, EPOCH)[0]
     assert np.abs(inp["xc"]).max() < 17 and np.abs(inp["xn"]).max() < 17
@@ -36,7 +44,7 @@ def test_operands_survive_fp16_and_bf16(geom):
             assert torch.equal(t.bfloat16().float(), t), what + ": bf16"
 
 
-@GEOMS
+@ALL
 def test_preactivations_are_exact_in_any_order_and_never_zero(geom):
     perm = np.random.RandomState(0).permutation(768)
     for name, x, W1, b1 in _encoder_operands(geom):
@@ -55,7 +63,7 @@ def test_preactivations_are_exact_in_any_order_and_never_zero(geom):
         assert mag.max() < 1024, (name, mag.max())
 
 
-@GEOMS
+@ALL
 def test_gates_are_open_and_mask_decisions_are_robust(geom):
     r = X.case(geom, EPOCH)[2]["oracle"]
     mask = np.asarray(r["mask"])
@@ -102,7 +110,7 @@ def _torch_step(inp, st, epoch):
 
 
 @pytest.mark.parametrize("epoch", [0, EPOCH])
-@GEOMS
+@ALL
 def test_fp32_references_lie_inside_the_fp32_bound(geom, epoch):
     inp, st, ref = X.case(geom, epoch)
     r = ref["oracle"]
@@ -147,7 +155,7 @@ def _ratio(dw, ref, prec):
     return X.worst(dw - ref["grads"][0], X.grad_limit("dW1", prec, ref))
 
 
-@GEOMS
+@ALL
 def test_simulated_16bit_scale_rounding_lies_inside_the_bound(geom):
     ref = X.case(geom, EPOCH)[2]
     assert _ratio(_dw1(ref), ref, "fp32") < 1e-6                 # the rebuild itself
@@ -193,4 +201,122 @@ def test_wrong_weight_gradients_exceed_the_fp16_bound_tenfold(geom):
     for what, dw in _mutants(geom):
         r = _ratio(dw, ref, "fp16")
         print("%s: %s: %.1f x the fp16 bound" % (X.geom_id(geom), what, r))
+        assert r >= 10.0, (what, r)
+
+
+# ---------------------------------------------------------------- the long problems' own controls
+# (X.LONG_GEOMS: past about 100 slabs one slab carries less of S_W1 than the bound allows, so the mutants above
+# would pass there; the sentinel channels give every slab a column it shares with only every 128th slab.)
+
+def _wg_slabs(geom, epoch=EPOCH):
+    """Every weight-gradient slab of a long problem in dad_wg_total's order: (s, branch, u, c, frames, loud), frames =
+    the slab's valid frames outside the temporal zero; loud = a clean or masked-in slab with at least 16 of them."""
+    inp, _, ref = X.case(geom, epoch)
+    c = X.cfg()
+    mlen = int(geom["Tn"] * c["TEMPORAL_MASK_RATIO"])
+    mask = np.asarray(ref["oracle"]["mask"]) > 0
+    for noisy, B, T, lens in ((False, geom["B"], geom["T"], geom["lens_c"]), (True, geom["Bn"], geom["Tn"], geom["lens_n"])):
+        for u in range(B):
+            live = np.arange(T) < lens[u]
+            if noisy:
+                live[int(inp["start"][u]):int(inp["start"][u]) + mlen] = False
+            for k in range((T + 31) // 32):
+                frames = int(live[32 * k:32 * k + 32].sum())
+                loud = frames >= 16 and (not noisy or bool(mask[u]))
+                yield X.wg_slab(geom["B"], geom["T"], geom["Bn"], geom["Tn"], noisy, u, k), "strong" if noisy else "clean", u, k, frames, loud
+
+
+@SENTINEL
+def test_sentinel_channels_hold_one_slab_in_128(geom):
+    inp = X.case(geom, EPOCH)[0]
+    xw, xs = X.augmented(inp, X.cfg())
+    assert np.all(inp["u"][X.SENT0:] == 1.0)
+    for s, branch, u, k, frames, _ in _wg_slabs(geom):
+        rows = slice(32 * k, 32 * k + 32)
+        own = X.SENT0 + s % X.SENT_N
+        for a in ((inp["xc"],) if branch == "clean" else (inp["xn"], inp["nw"], inp["ns"], xw, xs)):
+            sent = a[u, rows, X.SENT0:].copy()
+            sent[:, own - X.SENT0] = 0
+            assert not sent.any(), (s, branch)
+        x = inp["xc"] if branch == "clean" else inp["xn"]
+        pad = (inp["mc"] if branch == "clean" else inp["mn"])[u, rows]
+        v = x[u, rows, own]
+        assert np.all(v[pad] == 0) and np.all(np.abs(v[~pad]) >= 0.125) and np.all(np.abs(v[~pad]) <= 2.0), (s, branch)
+
+
+@SENTINEL
+def test_every_loud_slab_is_visible_in_the_weight_gradient(geom):
+    """Clearing a loud slab's ReLU' bits, and counting the slab twice, each move some dW1 element at least 10x
+    outside the fp16 bound."""
+    ref = X.case(geom, EPOCH)[2]
+    lim = X.grad_limit("dW1", "fp16", ref)
+    dw_ref = ref["grads"][0]
+    slabs = list(_wg_slabs(geom))
+    loud = [t for t in slabs if t[5]]
+    worst = {}
+    for s, branch, u, k, frames, _ in loud:
+        p = ref["parts"][branch]
+        rows = slice(32 * k, 32 * k + 32)
+        scale = p["g"][u] / max(p["vlen"][u], 1.0)
+        own = scale[:, None] * (p["act"][u, rows].astype(np.float64).T @ p["x"][u, rows].astype(np.float64))
+        for what, dw in (("dropped", dw_ref - own), ("twice", dw_ref + own)):
+            worst[(s, what)] = X.worst(dw - dw_ref, lim)
+    low = min(worst, key=worst.get)
+    print("%s: %d loud and %d silent slabs; a loud slab dropped or counted twice reads %.1f x to %.1f x the fp16 bound "
+          "(least: slab %d %s)" % (X.geom_id(geom), len(loud), len(slabs) - len(loud), worst[low], max(worst.values()),
+                                    low[0], low[1]))
+    assert loud and worst[low] >= 10.0, (low, worst[low])
+
+
+def test_l3_splits_begin_and_end_in_loud_slabs_and_its_mask_is_mixed():
+    geom = X.LONG["L3"]
+    mask = np.asarray(X.case(geom, EPOCH)[2]["oracle"]["mask"])
+    assert mask.min() == 0 and mask.max() == 1 and mask.sum() >= 8, mask
+    loud = {t[0]: t[5] for t in _wg_slabs(geom)}
+    assert len(loud) == 22 * 64
+    for split in range(22):
+        assert loud[64 * split] and loud[64 * split + 63], split
+
+
+def _slab_partials(x, pad, W1, b1):
+    """The encoder's per-slab pooled sums and active counts [B, ceil(T / 32), H] in float64, and the lengths."""
+    pre = X.preact64(x, W1, b1)
+    act = (pre > 0) & ~pad[..., None]
+    B, T, H = pre.shape
+    nc = (T + 31) // 32
+    r, a = np.zeros((B, 32 * nc, H)), np.zeros((B, 32 * nc, H))
+    r[:, :T], a[:, :T] = np.where(act, pre, 0.0), act
+    return r.reshape(B, nc, 32, H).sum(2), a.reshape(B, nc, 32, H).sum(2), (~pad).sum(1).astype(np.float64)
+
+
+# what csrc/pool.h's loops could get wrong past 16 slabs / 512 frames, as (name, slabs summed of nc, frames counted of T)
+_POOL_MUTANTS = (("only the first 16 slabs summed", lambda nc: slice(0, 16), None),
+                 ("the last slab left out", lambda nc: slice(0, nc - 1), None),
+                 ("the length stops counting at frame 512", lambda nc: slice(0, nc), 512))
+
+
+@POOLED
+def test_pool_mutants_past_16_slabs_exceed_the_bounds_tenfold(geom):
+    inp, st, ref = X.case(geom, EPOCH)
+    pads = {"clean": inp["mc"], "weak": inp["mn"], "strong": inp["mn"]}
+    names = {"clean": "e_clean", "weak": "e_teacher", "strong": "e_strong"}
+    parts = {name: _slab_partials(x, pads[name], W1, b1) for name, x, W1, b1 in _encoder_operands(geom)}
+    for name, (ps, pc, vlen) in parts.items():        # the rebuild itself
+        e = ps.sum(1) / np.maximum(vlen, 1.0)[:, None]
+        assert X.worst(e - ref["e"][names[name]], X.bound("e", None, ref["T"][names[name]]) * np.abs(e)) < 1e-6
+    for what, take, stop in _POOL_MUTANTS:
+        db1 = np.zeros(ref["grads"][1].shape)
+        for name, (ps, pc, vlen) in parts.items():
+            sel = take(ps.shape[1])
+            n = vlen if stop is None else np.minimum(vlen, stop)
+            e = ps[:, sel].sum(1) / np.maximum(n, 1.0)[:, None]
+            er = ref["e"][names[name]]
+            r = X.worst(e - er, X.bound("e", None, ref["T"][names[name]]) * np.abs(er))
+            print("%s: %s: %s %.0f x its bound" % (X.geom_id(geom), what, names[name], r))
+            assert r >= 10.0, (what, name, r)
+            if name != "weak":      # cnt_tot and the length the kernel stores feed db1 = sum_u dL/de_u / len_u * count_u
+                p = ref["parts"][name]
+                db1 += ((p["g"] / np.maximum(n, 1.0)[:, None]) * pc[:, sel].sum(1)).sum(0)
+        r = X.worst(db1 - ref["grads"][1], X.grad_limit("db1", "fp16", ref))
+        print("%s: %s: db1 %.0f x its bound" % (X.geom_id(geom), what, r))
         assert r >= 10.0, (what, r)
