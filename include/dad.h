@@ -719,6 +719,69 @@ int dad_eval_noise(const dad_noise_args* args, void* workspace, void* stream);
  * NULL; DAD_E_SHAPE as above (levels taken as 1). */
 int dad_eval_noise_draws(const dad_noise_args* args, float* out, void* stream);
 
+/* --- input gradients of a split: the worst-case direction, store-fed (csrc/input_grad.hip) ----
+ * dad_eval_noise measures a split under RANDOM noise.  dad_input_grad gives the direction of the WORST perturbation
+ * of the same size: the vector-Jacobian product of the eval-mode forward (SSRLModel.predict, I/model.py:225-245)
+ * with respect to the stored rows, which the reference's autograd never forms (its inputs do not require grad).
+ *
+ * Definition.  For utterance u with len frames x_t, an optional perturbation delta_t and the caller's logit
+ * cotangent dz_u[4]:
+ *   pre_tj = W1[j] . (x_t + delta_t) + b1[j],   m_tj = pre_tj > 0   (torch's ReLU': 0 at 0)
+ *   s_u[j] = sum_c W2[c][j] dz_u[c],            g_u = s_u / max(len, 1)
+ *   G_t[d] = sum_j m_tj g_u[j] W1[j][d]
+ *   step_t[d] = clamp(delta_t[d] + alpha sgn(G_t[d]), -radius, +radius),   sgn(0) = 0, delta = 0 when NULL
+ * With dz = softmax(z) - onehot(target), G is the gradient of PLAIN cross-entropy of the utterance with respect to
+ * its frames (not of the trainer's label-smoothed loss), the step with delta = NULL is FGSM (Goodfellow et al. 2015)
+ * and iterating it with delta_out fed back as delta_in is PGD (Madry et al. 2018).
+ *
+ * Layout.  delta_in, grad and delta_out are float [32 * slabs][768] in dad_eval_noise's explicit layout: frame t of
+ * utterance i is row 32 * slab_off[i] + t, so a delta_out is a `noise` of dad_eval_noise as it stands; frame_l1 is
+ * float [32 * slabs] with sum_d |G_t[d]| (fp32, a fixed order) in the same rows.  Rows past an utterance's length
+ * are written 0 in every output, so no buffer needs initialising; a length-0 utterance owns no slab and writes
+ * nothing.  All three outputs are optional (NULL = not written).  delta_out may be delta_in itself: every element is
+ * read and written by the same lane.  A G element that is not finite takes step 0 and is counted.
+ *
+ * Precision.  DAD_PREC_FP32: exact-f32 MFMA for both GEMMs; g_u in fp32 (one product and three fmas over c, then the
+ * division).  DAD_PREC_FP16: x + delta is summed in f32 and rounded once to fp16, W1 is rounded to fp16 (a row-major
+ * and a transposed copy in the workspace), and the backward A operand is m (.) (c_u s_u) rounded to fp16 with c_u the
+ * power of two that puts max_j |s_u[j]| into [2^14, 2^15) (g_u of a long utterance would fall into fp16's subnormals
+ * otherwise); fp32 accumulation, and 1 / c_u and 1 / max(len, 1) are applied in fp32 after the GEMM.
+ * Bit identities.  With delta_in == NULL the forward accumulators hold dad_eval_split's bits (the same loaders and
+ * k order); delta_in == NULL equals a delta_in of zeros; the result depends on neither the order of the utterances
+ * nor the slab-to-workgroup assignment; two calls on the same inputs write the same bits (integer atomics only). */
+#define DAD_IG_FRAMES 0         /* frames processed (the sum of lens) */
+#define DAD_IG_NONFINITE 1      /* elements of G, over those frames, that are not finite */
+#define DAD_IG_ZERO 2           /* elements of G, over those frames, that equal 0 */
+#define DAD_IG_COUNTS 4         /* int64 slots of the counts block (3 reserved, written 0) */
+/* Rows as dad_eval_args (store, rows, lens, slab_off, slabs).  One network per call.  Enqueue only, no allocation,
+ * no device read on the host; the call itself zeroes counts. */
+typedef struct dad_input_grad_args {
+  const void* store;            /* [frames][768], dtype store_dtype */
+  const int64_t* rows;          /* [n] store row of frame 0 */
+  const int32_t* lens;          /* [n] frames */
+  const int32_t* slab_off;      /* [n + 1] exclusive prefix of ceil(lens / 32) */
+  const float* params;          /* [DAD_NPARAM] flat [W1|b1|W2|b2] */
+  const float* dz;              /* [n][4] logit cotangents, required */
+  const float* delta_in;        /* [32 * slabs][768] or NULL: no perturbation */
+  float* grad;                  /* [32 * slabs][768] */
+  float* delta_out;             /* [32 * slabs][768]; may alias delta_in */
+  float* frame_l1;              /* [32 * slabs] */
+  int64_t* counts;              /* [DAD_IG_COUNTS], required */
+  int64_t n;                    /* utterances, >= 1 */
+  int64_t slabs;                /* slab_off[n] */
+  float alpha;                  /* step size, finite */
+  float radius;                 /* clamp radius, >= 0; INFINITY = no clamp */
+  int32_t store_dtype;          /* DAD_STORE_* */
+  int32_t precision;            /* DAD_PREC_FP32 or DAD_PREC_FP16 */
+} dad_input_grad_args;
+/* workspace bytes of dad_input_grad: the two fp16 copies of W1 in DAD_PREC_FP16, one aligned unit otherwise (0 for
+ * unsupported sizes); no initialisation needed */
+size_t dad_input_grad_workspace_bytes(int64_t n, int64_t slabs, int precision);
+/* Checked on the host before anything is launched.  DAD_E_ARG: args, workspace or a required pointer is NULL, an
+ * unknown dtype / precision, alpha not finite, radius negative or NaN; DAD_E_SHAPE: n < 1 or slabs outside
+ * [0, n * 2^26]; DAD_E_UNSUPPORTED: DAD_PREC_BF16. */
+int dad_input_grad(const dad_input_grad_args* args, void* workspace, void* stream);
+
 /* --- class separation of a split's embeddings (csrc/cluster.hip) -------------------------
  * calculate_cluster_metrics (I/iemocap_plot_tsne.py:390-398): scikit-learn's silhouette_score and
  * calinski_harabasz_score of emb [n][256] (dad_eval_split's emb / t_emb) under labels [n], whose

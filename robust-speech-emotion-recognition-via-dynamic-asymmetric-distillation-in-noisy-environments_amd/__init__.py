@@ -27,6 +27,8 @@ from .evaluate import (duration_report, early_decision_curve, enqueue_eval_windo
                        window_frames, windows, windows_host)
 from .evaluate import (enqueue_eval_noise, evaluate_noise_store, noise_draws, noise_response_curve,
                        robustness_report)
+from .evaluate import (adversarial_response_curve, enqueue_input_grad, evaluate_adversarial_store, input_gradients,
+                       worst_case_report)
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
            "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "SupervisedContrastiveLoss", "TrainingTrace",
@@ -37,6 +39,8 @@ __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "D
            "windows", "windows_host", "window_frames", "enqueue_eval_windows", "evaluate_windows_store",
            "early_decision_curve", "duration_report",
            "noise_draws", "enqueue_eval_noise", "evaluate_noise_store", "noise_response_curve", "robustness_report",
+           "enqueue_input_grad", "input_gradients", "evaluate_adversarial_store", "adversarial_response_curve",
+           "worst_case_report",
            "build", "lib"]
 
 

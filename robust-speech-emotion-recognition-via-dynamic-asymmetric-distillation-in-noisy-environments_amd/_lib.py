@@ -86,6 +86,9 @@ EN_CONF, EN_FLIPS, EN_SURVIVE = 0, 128, 136
 EN_N, EN_N_LABELLED, EN_N_SKIPPED, EN_N_NONFINITE, EN_LEVELS, EN_COUNTS = 144, 145, 146, 147, 148, 160
 EN_SUM_SCORE, EN_SUM_DRIFT, EN_SUM_KL, EN_SUMS = 0, 8, 16, 24
 
+# dad_input_grad (dad.h DAD_IG_*): the int64 slots of the counts block
+IG_FRAMES, IG_NONFINITE, IG_ZERO, IG_COUNTS = 0, 1, 2, 4
+
 
 class DadConfig(ctypes.Structure):
     _fields_ = [
@@ -179,6 +182,14 @@ class DadNoiseArgs(ctypes.Structure):
                 + [(n, ctypes.c_int32) for n in ("levels", "store_dtype", "use_entropy", "precision")])
 
 
+class DadInputGradArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_void_p) for n in
+                 ("store", "rows", "lens", "slab_off", "params", "dz", "delta_in", "grad", "delta_out", "frame_l1",
+                  "counts")]
+                + [("n", ctypes.c_int64), ("slabs", ctypes.c_int64), ("alpha", ctypes.c_float), ("radius", ctypes.c_float),
+                   ("store_dtype", ctypes.c_int32), ("precision", ctypes.c_int32)])
+
+
 class DadTsneArgs(ctypes.Structure):
     _fields_ = [("max_iter", ctypes.c_int32), ("n_iter_without_progress", ctypes.c_int32),
                 ("early_exaggeration", ctypes.c_double), ("learning_rate", ctypes.c_double),
@@ -262,6 +273,8 @@ EXPORTS = {
     "dad_eval_noise_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     "dad_eval_noise": (ctypes.c_int, [ctypes.POINTER(DadNoiseArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "dad_eval_noise_draws": (ctypes.c_int, [ctypes.POINTER(DadNoiseArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_input_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "dad_input_grad": (ctypes.c_int, [ctypes.POINTER(DadInputGradArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "dad_augment": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -355,7 +368,8 @@ OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_step_plan_kernels", "dad_trace_
                     "dad_knn_vote", "dad_trustworthiness", "dad_trustworthiness_chunked",
                     "dad_scl_workspace_bytes", "dad_scl_plan", "dad_scl", "dad_scl_chunked",
                     "dad_eval_windows_workspace_bytes", "dad_eval_windows",
-                    "dad_eval_noise_workspace_bytes", "dad_eval_noise", "dad_eval_noise_draws")
+                    "dad_eval_noise_workspace_bytes", "dad_eval_noise", "dad_eval_noise_draws",
+                    "dad_input_grad_workspace_bytes", "dad_input_grad")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

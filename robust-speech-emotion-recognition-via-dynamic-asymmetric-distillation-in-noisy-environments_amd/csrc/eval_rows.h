@@ -369,6 +369,95 @@ __device__ __forceinline__ void eval_slab_noise_f16(const void* store, size_t xe
   }
 }
 
+// ---- an explicit perturbation added to the rows before the GEMM (input_grad.hip) ---------------------------
+// The 8 channels of a Raw8 chunk widened to f32 (the values Raw4::get gives for the same channels)
+template <int DT>
+__device__ __forceinline__ void raw8_widen(const Raw8<DT>& r, f32x4& a, f32x4& b) {
+  if constexpr (DT == DAD_STORE_F32) {
+    a = r.a; b = r.b;
+  } else if constexpr (DT == DAD_STORE_F16) {
+    a[0] = Raw4<DAD_STORE_F16>::h(r.v[0] & 0xffffu); a[1] = Raw4<DAD_STORE_F16>::h(r.v[0] >> 16);
+    a[2] = Raw4<DAD_STORE_F16>::h(r.v[1] & 0xffffu); a[3] = Raw4<DAD_STORE_F16>::h(r.v[1] >> 16);
+    b[0] = Raw4<DAD_STORE_F16>::h(r.v[2] & 0xffffu); b[1] = Raw4<DAD_STORE_F16>::h(r.v[2] >> 16);
+    b[2] = Raw4<DAD_STORE_F16>::h(r.v[3] & 0xffffu); b[3] = Raw4<DAD_STORE_F16>::h(r.v[3] >> 16);
+  } else {
+    a[0] = __uint_as_float(r.v[0] << 16); a[1] = __uint_as_float(r.v[0] & 0xffff0000u);
+    a[2] = __uint_as_float(r.v[1] << 16); a[3] = __uint_as_float(r.v[1] & 0xffff0000u);
+    b[0] = __uint_as_float(r.v[2] << 16); b[1] = __uint_as_float(r.v[2] & 0xffff0000u);
+    b[2] = __uint_as_float(r.v[3] << 16); b[3] = __uint_as_float(r.v[3] & 0xffff0000u);
+  }
+}
+
+// eval_slab_f32 (one network) on the rows x + delta: delta is an explicit f32 array in the slab-aligned layout of
+// dad_eval_noise and del the element of the lane's first channel.  The sum is formed in f32 ahead of the MFMA, in
+// eval_slab_f32's k order.
+template <int DT>
+__device__ __forceinline__ void eval_slab_delta_f32(const void* store, size_t xel, const float* delta, size_t del,
+                                                    const float* W, f32x16 (&acc)[DAD_HT]) {
+  Raw4<DT> xc, xn;
+  f32x4 dc, dn;
+  f32x4 wc[DAD_HT], wn[DAD_HT];
+  xc.load(store, xel);
+  dc = *reinterpret_cast<const f32x4*>(delta + del);
+#pragma unroll
+  for (int ht = 0; ht < DAD_HT; ++ht) wc[ht] = *reinterpret_cast<const f32x4*>(W + (size_t)ht * 32 * DAD_D);
+  for (int d0 = 0; d0 < DAD_D; d0 += 8) {
+    const int dn_ = d0 + 8 < DAD_D ? d0 + 8 : d0;   // the last step reloads itself
+    xn.load(store, xel + dn_);
+    dn = *reinterpret_cast<const f32x4*>(delta + del + dn_);
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht) wn[ht] = *reinterpret_cast<const f32x4*>(W + (size_t)ht * 32 * DAD_D + dn_);
+    __builtin_amdgcn_sched_barrier(0);
+    const f32x4 x = xc.get() + dc;
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[ht] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[e], wc[ht][e], acc[ht], 0, 0, 0);
+    xc = xn;
+    dc = dn;
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht) wc[ht] = wn[ht];
+  }
+}
+
+// eval_slab_f16 (one network) on the rows x + delta: the f32 sum of the widened row and delta is rounded once to
+// fp16
+template <int DT>
+__device__ __forceinline__ void eval_slab_delta_f16(const void* store, size_t xel, const float* delta, size_t del,
+                                                    const uint16_t* W, f32x16 (&acc)[DAD_HT]) {
+  Raw8<DT> xc, xn;
+  f32x4 dc[2], dn[2];
+  u32x4 wc[DAD_HT], wn[DAD_HT];
+  xc.load(store, xel);
+  dc[0] = *reinterpret_cast<const f32x4*>(delta + del);
+  dc[1] = *reinterpret_cast<const f32x4*>(delta + del + 4);
+#pragma unroll
+  for (int ht = 0; ht < DAD_HT; ++ht) wc[ht] = *reinterpret_cast<const u32x4*>(W + (size_t)ht * 32 * DAD_D);
+  for (int d0 = 0; d0 < DAD_D; d0 += 16) {
+    const int dn_ = d0 + 16 < DAD_D ? d0 + 16 : d0;
+    xn.load(store, xel + dn_);
+    dn[0] = *reinterpret_cast<const f32x4*>(delta + del + dn_);
+    dn[1] = *reinterpret_cast<const f32x4*>(delta + del + dn_ + 4);
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht) wn[ht] = *reinterpret_cast<const u32x4*>(W + (size_t)ht * 32 * DAD_D + dn_);
+    __builtin_amdgcn_sched_barrier(0);
+    f32x4 a, b;
+    raw8_widen<DT>(xc, a, b);
+    a += dc[0];
+    b += dc[1];
+    const f16x8 x = __builtin_bit_cast(f16x8, u32x4{dad_pack2<true>(a[0], a[1]), dad_pack2<true>(a[2], a[3]),
+                                                    dad_pack2<true>(b[0], b[1]), dad_pack2<true>(b[2], b[3])});
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht)
+      acc[ht] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, __builtin_bit_cast(f16x8, wc[ht]), acc[ht], 0, 0, 0);
+    xc = xn;
+    dc[0] = dn[0];
+    dc[1] = dn[1];
+#pragma unroll
+    for (int ht = 0; ht < DAD_HT; ++ht) wc[ht] = wn[ht];
+  }
+}
+
 // eval_epilogue on acc0 + sigma[k] acc1 for every level k -> part[k][256] (one fma; sigma = 0 with a finite acc1
 // leaves eval_epilogue's bits).  MAXK >= levels.  The level loop is unrolled into straight-line code behind
 // wave-uniform branches, one h tile at a time, so the accumulators are copied to VALU registers 32 at a time next

@@ -48,6 +48,13 @@ and the response to additive noise, every noise level of a draw in one pass (dad
   noise_draws, enqueue_eval_noise, evaluate_noise_store, noise_response_curve, robustness_report
                       SSRLModel.predict / get_embeddings on x + sigma * N, the perturbation of
                       DataAugmentation.weak_augment / strong_augment's noise term (I/utils.py:328-350)
+
+and the worst perturbation of the same size, the gradient with respect to the stored rows (dad_input_grad,
+csrc/input_grad.hip):
+
+  enqueue_input_grad, input_gradients, evaluate_adversarial_store, adversarial_response_curve, worst_case_report
+                      not in the reference (its inputs do not require grad): autograd of SSRLModel.predict with respect
+                      to x, FGSM (Goodfellow et al. 2015) and PGD (Madry et al. 2018)
 """
 import warnings
 
@@ -1676,3 +1683,292 @@ def robustness_report(initial_model, trained_model, store_or_loader, sigmas=None
     """robustness_from_curves of noise_response_curve under the initial and the trained weights, on the same draws."""
     return robustness_from_curves(noise_response_curve(initial_model, store_or_loader, sigmas, draws),
                                   noise_response_curve(trained_model, store_or_loader, sigmas, draws))
+
+
+# ---- the worst-case perturbation: input gradients, FGSM and PGD (dad_input_grad, csrc/input_grad.hip) -------------
+_IG_OUTPUTS = ("grad", "delta", "frame_l1")
+_ADV_MAX_EPS = _lib.EN_MAX_LEVELS - 1
+_TARGETS = ("label", "pred")
+
+
+def _ig_buffers(plan):
+    """The buffers of dad_input_grad over this split, kept on the plan beside the noise buffers: {'counts_d' /
+    'counts_h' the DAD_IG_* block and its pinned host copy, 'ws' the workspace, 'row_utt' the utterance of every row
+    of the explicit layout}."""
+    b = plan._noise.get("input_grad")
+    if b is None:
+        nslab = (plan.slab_off_d[1:] - plan.slab_off_d[:-1]).to(torch.int64)
+        b = {"counts_d": torch.zeros(_lib.IG_COUNTS, dtype=torch.int64, device=plan.device),
+             "counts_h": torch.zeros(_lib.IG_COUNTS, dtype=torch.int64).pin_memory(), "ws": None,
+             "row_utt": torch.repeat_interleave(torch.arange(plan.n, device=plan.device), 32 * nslab)}
+        plan._noise["input_grad"] = b
+    return b
+
+
+def _explicit_tensor(plan, t, what):
+    if (t.dtype != torch.float32 or t.device != plan.device or not t.is_contiguous()
+            or tuple(t.shape) != (32 * plan.slabs, 768)):
+        raise ValueError("%s must be a contiguous float32 [%d, 768] tensor on %s" % (what, 32 * plan.slabs, plan.device))
+    return t
+
+
+def enqueue_input_grad(model, plan, dz, delta=None, alpha=1.0, radius=float("inf"), use_teacher=False,
+                       precision="fp32", outputs=("delta",), _delta_out=None, _counts=None):
+    """dad_input_grad on the current stream, enqueue only (no copy, no synchronisation; graph-capturable): for the
+    logit cotangents dz [n, 4] (float32, on the device) the gradient G of sum_u dz_u . z_u with respect to the
+    stored frames, taken at x + delta, and the signed step clamp(delta + alpha * sgn(G), -radius, +radius).  delta
+    is None or a float32 [32 * slabs, 768] device tensor in noise_draws' layout (frame t of utterance i in row
+    32 * slab_off[i] + t).  outputs: 'grad' and 'delta' [32 * slabs, 768], 'frame_l1' [32 * slabs]; rows past an
+    utterance's length are 0.  With a `delta` given, 'delta' is that tensor, updated in place.  The DAD_IG_* counts
+    land in the plan's block.  Every tensor of the explicit layout is float32, 3 KB per frame: about 4 GB for a
+    split of 5,531 utterances, per tensor.  Returns the {name: device tensor} of the requested outputs."""
+    prec = _PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    dev = plan.device
+    if model.student_flat.device != dev:
+        raise RuntimeError("model on %s, store on %s" % (model.student_flat.device, dev))
+    alpha, radius = float(alpha), float(radius)
+    if not np.isfinite(alpha):
+        raise ValueError("alpha must be finite, got %r" % alpha)
+    if not radius >= 0:
+        raise ValueError("radius must be >= 0 (inf: no clamp), got %r" % radius)
+    if dz.dtype != torch.float32 or dz.device != dev or not dz.is_contiguous() or tuple(dz.shape) != (plan.n, 4):
+        raise ValueError("dz must be a contiguous float32 [%d, 4] tensor on %s" % (plan.n, dev))
+    if delta is not None:
+        _explicit_tensor(plan, delta, "delta")
+    out = {}
+    for name in outputs:
+        if name not in _IG_OUTPUTS:
+            raise ValueError("unknown output %r (one of %s)" % (name, ", ".join(_IG_OUTPUTS)))
+        if name == "frame_l1":
+            out[name] = torch.empty((32 * plan.slabs,), dtype=torch.float32, device=dev)
+        elif name == "delta" and _delta_out is not None:
+            out[name] = _explicit_tensor(plan, _delta_out, "_delta_out")
+        elif name == "delta" and delta is not None:
+            out[name] = delta
+        else:
+            out[name] = torch.empty((32 * plan.slabs, 768), dtype=torch.float32, device=dev)
+    fn = _lib.require("dad_input_grad", "the input gradients")
+    b = _ig_buffers(plan)
+    need = int(_lib.require("dad_input_grad_workspace_bytes", "the input gradients")(plan.n, plan.slabs, prec))
+    if b["ws"] is None or b["ws"].numel() < need:
+        b["ws"] = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    counts = b["counts_d"] if _counts is None else _counts
+    store = plan.store
+    a = _lib.DadInputGradArgs()
+    a.store = store.feats.data_ptr()
+    a.rows, a.lens, a.slab_off = plan.rows_d.data_ptr(), plan.lens_d.data_ptr(), plan.slab_off_d.data_ptr()
+    a.params = (model.teacher_flat if use_teacher else model.student_flat).data_ptr()
+    a.dz = dz.data_ptr()
+    a.delta_in = None if delta is None else (delta.data_ptr() or None)
+    a.grad = out["grad"].data_ptr() or None if "grad" in out else None
+    a.delta_out = out["delta"].data_ptr() or None if "delta" in out else None
+    a.frame_l1 = out["frame_l1"].data_ptr() or None if "frame_l1" in out else None
+    a.counts = counts.data_ptr()
+    a.n, a.slabs = plan.n, plan.slabs
+    a.alpha, a.radius = alpha, radius
+    a.store_dtype = STORE_DTYPES[store.feats.dtype]
+    a.precision = prec
+    _lib.check(fn(a, _lib.ptr(b["ws"]), torch.cuda.current_stream(dev).cuda_stream), "dad_input_grad")
+    return out
+
+
+def _adv_target(plan, pred, target):
+    """The class each utterance's cross-entropy is taken against: its label where that lies in [0, 4), the network's
+    own clean prediction otherwise; 'pred' uses the prediction everywhere."""
+    if target == "pred":
+        return pred
+    lab = plan.labels_d
+    return torch.where((lab >= 0) & (lab < 4), lab, pred)
+
+
+def _adv_check(plan, target):
+    if target not in _TARGETS:
+        raise ValueError("unknown target %r (one of %s)" % (target, ", ".join(_TARGETS)))
+    if target == "label" and plan.labels_d is None:
+        raise ValueError("the split has no labels: target='label' needs them (or use target='pred')")
+
+
+def _ce_cotangent(logits, tgt):
+    """softmax(z) - onehot(target): the gradient of plain (not label-smoothed) cross-entropy with respect to z"""
+    return (torch.softmax(logits, dim=1) - torch.nn.functional.one_hot(tgt, 4).to(torch.float32)).contiguous()
+
+
+def _read_ig_counts(plan, counts_d=None):
+    b = _ig_buffers(plan)
+    b["counts_h"].copy_(b["counts_d"] if counts_d is None else counts_d, non_blocking=True)
+    torch.cuda.current_stream(plan.device).synchronize()
+    c = b["counts_h"].numpy().copy()
+    if c[_lib.IG_NONFINITE] > 0:
+        raise _lib.DadError("dad_input_grad: %d gradient element(s) are not finite (fp16: an operand beyond +-65504; any "
+                            "precision: non-finite features or cotangents)" % c[_lib.IG_NONFINITE])
+    return {"frames": int(c[_lib.IG_FRAMES]), "n_nonfinite_grad": int(c[_lib.IG_NONFINITE]),
+            "n_zero_grad": int(c[_lib.IG_ZERO])}
+
+
+def input_gradients(model, store_or_loader, target="label", use_teacher=False, precision="fp32"):
+    """The gradient of each utterance's plain cross-entropy against `target` ('label', or 'pred': the network's own
+    prediction) with respect to its stored frames: one dad_eval_split, the cotangent softmax(z) - onehot(target) on
+    the device, one dad_input_grad.  Returns {'grad' [32 * slabs, 768] and 'frame_l1' [32 * slabs] (sum_d |G_t[d]|:
+    which frames the decision hangs on) in noise_draws' layout, 'utt_l1' [n] (sum |G| of an utterance: the
+    first-order loss increase per unit of an L-infinity perturbation), 'target' [n], 'dz' [n, 4], 'frames',
+    'n_nonfinite_grad', 'n_zero_grad'}.  'grad' is float32, 3 KB per frame (about 4 GB for 5,531 utterances).
+    Raises DadError on a gradient element that is not finite."""
+    model.eval()
+    plan = EvalPlan.of(store_or_loader)
+    _adv_check(plan, target)
+    lname, pname = ("t_logits", "t_pred") if use_teacher else ("logits", "pred")
+    ev = enqueue_eval_split(model, plan, use_teacher, True, precision, (lname, pname))
+    tgt = _adv_target(plan, ev[pname], target)
+    dz = _ce_cotangent(ev[lname], tgt)
+    out = enqueue_input_grad(model, plan, dz, None, 0.0, float("inf"), use_teacher, precision, ("grad", "frame_l1"))
+    utt = torch.zeros(plan.n, dtype=torch.float32, device=plan.device)
+    utt.index_add_(0, _ig_buffers(plan)["row_utt"], out["frame_l1"])
+    res = _read_ig_counts(plan)
+    res.update(grad=out["grad"], frame_l1=out["frame_l1"], utt_l1=utt, target=tgt, dz=dz)
+    return res
+
+
+def _adv_epsilons(epsilons):
+    e = [float(v) for v in np.asarray(epsilons, dtype=np.float64).reshape(-1)]
+    if not 1 <= len(e) <= _ADV_MAX_EPS:
+        raise ValueError("between 1 and %d epsilons, got %d (level 0 is the clean base)" % (_ADV_MAX_EPS, len(e)))
+    if any(not np.isfinite(v) or v < 0 for v in e):
+        raise ValueError("epsilons must be finite and >= 0, got %r" % (e,))
+    return e
+
+
+def _adv_result(res, eps):
+    res.pop("sigmas")
+    res["epsilons"] = [0.0] + list(eps)
+    for lv in res["levels"]:
+        lv["epsilon"] = lv.pop("sigma")
+    return res
+
+
+def evaluate_adversarial_store(model, plan_or_store, epsilons, steps=1, alpha=None, target="label", use_teacher=False,
+                               precision="fp32", outputs=()):
+    """The split under the worst-case perturbation of L-infinity size epsilon, for up to 7 epsilons.  The loss is the
+    plain cross-entropy against `target` (the label where it lies in [0, 4), the clean prediction otherwise; 'pred':
+    the prediction everywhere), not the trainer's label-smoothed one.
+
+    steps == 1 with alpha None is FGSM (Goodfellow et al. 2015): one dad_eval_split, one dad_input_grad for the
+    direction sgn(dL/dx), then ONE dad_eval_noise(noise=direction, sigmas=(0, eps_1 .. eps_K)): the encoder is linear
+    before its ReLU, so a fixed direction at several epsilons costs what one noise draw at several sigmas does.
+    Otherwise PGD (Madry et al. 2018), per epsilon: delta_0 = 0; `steps` times the logits at x + delta_j
+    (dad_eval_noise(noise=delta_j, sigmas=(1,))), their cotangent, and delta_{j+1} = clamp(delta_j + alpha *
+    sgn(G(x + delta_j)), +-eps) in place; then one dad_eval_noise(noise=delta, sigmas=(0, 1)).  alpha defaults to
+    2.5 * eps / steps.
+
+    Returns evaluate_noise_store's dict with 'epsilons' (level 0 is the clean base, epsilon 0) in place of 'sigmas'
+    and 'epsilon' in place of each level's 'sigma', plus 'n_nonfinite_grad' and 'n_zero_grad', and a device tensor per
+    name in `outputs` (enqueue_eval_noise's, level-major over the K + 1 levels, and 'direction': FGSM's sign tensor
+    [32 * slabs, 768], or the list of PGD's final delta per epsilon).  The direction is materialised as float32, 3 KB
+    per frame: about 4 GB for a split of 5,531 utterances.  Raises DadError on non-finite logits or gradients."""
+    model.eval()
+    plan = EvalPlan.of(plan_or_store)
+    _adv_check(plan, target)
+    eps = _adv_epsilons(epsilons)
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("steps must be >= 1")
+    want_dir = "direction" in outputs
+    outputs = tuple(o for o in outputs if o != "direction")
+    for name in outputs:
+        if name != "break_level" and name not in _NOISE_OUTPUTS:
+            raise ValueError("unknown output %r (one of %s, break_level, direction)" % (name, ", ".join(_NOISE_OUTPUTS)))
+    dev = plan.device
+    if model.student_flat.device != dev:
+        raise RuntimeError("model on %s, store on %s" % (model.student_flat.device, dev))
+    lname, pname = ("t_logits", "t_pred") if use_teacher else ("logits", "pred")
+    ev = enqueue_eval_split(model, plan, use_teacher, True, precision, (lname, pname))
+    tgt = _adv_target(plan, ev[pname], target)
+    if steps == 1 and alpha is None:
+        direction = enqueue_input_grad(model, plan, _ce_cotangent(ev[lname], tgt), None, 1.0, float("inf"),
+                                       use_teacher, precision, ("delta",))["delta"]
+        grad_counts = _read_ig_counts(plan)
+        res = evaluate_noise_store(model, plan, [0.0] + eps, 0, 0, use_teacher, True, precision, outputs, direction)
+        res = _adv_result(res, eps)
+        res.update(grad_counts)
+        if want_dir:
+            res["direction"] = direction
+        return res
+
+    total = torch.zeros(_lib.IG_COUNTS, dtype=torch.int64, device=dev)
+    delta = torch.empty((32 * plan.slabs, 768), dtype=torch.float32, device=dev)
+    want = tuple(dict.fromkeys(tuple(o for o in outputs if o != "break_level") + ("pred",)))
+    runs, finals = [], []
+    for e in eps:
+        a = 2.5 * e / steps if alpha is None else float(alpha)
+        delta.zero_()
+        for _ in range(steps):
+            z = enqueue_eval_noise(model, plan, (1.0,), 0, 0, use_teacher, True, precision, ("logits",), delta)["logits"]
+            enqueue_input_grad(model, plan, _ce_cotangent(z[0], tgt), delta, a, e, use_teacher, precision, ("delta",))
+            total += _ig_buffers(plan)["counts_d"]
+        runs.append(evaluate_noise_store(model, plan, (0.0, 1.0), 0, 0, use_teacher, True, precision, want, delta))
+        if want_dir:
+            finals.append(delta.clone())
+    grad_counts = _read_ig_counts(plan, total)
+    # one block over the K + 1 levels: level 0 of the first run, level 1 of every run
+    K = len(eps) + 1
+    host = np.zeros(_NOISE_WORDS, dtype=np.int64)
+    counts, sums = host[:_lib.EN_COUNTS], host[_lib.EN_COUNTS:].view(np.float64)
+    preds = torch.cat([runs[0]["pred"][0:1]] + [r["pred"][1:2] for r in runs])
+    moved = preds != preds[0:1]
+    brk = torch.where(moved.any(0), moved.to(torch.int32).argmax(0).to(torch.int32),
+                      torch.full((plan.n,), K, dtype=torch.int32, device=dev))
+    survive = (brk[None, :] > torch.arange(K, device=dev, dtype=torch.int32)[:, None]).sum(1).cpu().numpy()
+    for k in range(K):
+        r, j = (runs[0], 0) if k == 0 else (runs[k - 1], 1)
+        rc, rs = r["block"][:_lib.EN_COUNTS], r["block"][_lib.EN_COUNTS:].view(np.float64)
+        counts[_lib.EN_CONF + 16 * k:_lib.EN_CONF + 16 * k + 16] = rc[_lib.EN_CONF + 16 * j:_lib.EN_CONF + 16 * j + 16]
+        counts[_lib.EN_FLIPS + k] = rc[_lib.EN_FLIPS + j]
+        counts[_lib.EN_SURVIVE + k] = survive[k]
+        for slot in (_lib.EN_SUM_SCORE, _lib.EN_SUM_DRIFT, _lib.EN_SUM_KL):
+            sums[slot + k] = rs[slot + j]
+    rc = runs[0]["block"]
+    for slot in (_lib.EN_N, _lib.EN_N_LABELLED, _lib.EN_N_SKIPPED):
+        counts[slot] = rc[slot]
+    counts[_lib.EN_N_NONFINITE] = max(int(r["n_nonfinite"]) for r in runs)
+    counts[_lib.EN_LEVELS] = K
+    res = _adv_result(_noise_block(host, [0.0] + eps), eps)
+    res.update(grad_counts)
+    for name in outputs:
+        if name == "break_level":
+            res[name] = brk
+        else:
+            res[name] = torch.cat([runs[0][name][0:1]] + [r[name][1:2] for r in runs])
+    if want_dir:
+        res["direction"] = finals
+    return res
+
+
+def adversarial_response_curve(model, store_or_loader, epsilons=None, steps=1, alpha=None, target="label",
+                               use_teacher=False, precision="fp32", cfg=None):
+    """noise_response_curve's shape for the worst-case perturbation: epsilons=None means default_noise_levels(cfg), so
+    the curve shares its axis with noise_response_curve (a leading 0 is the clean base level and is not attacked).
+    Returns {'sigmas' (the axis: 0 and the epsilons), 'epsilons', 'draws': 1, per level lists 'accuracy',
+    'balanced_accuracy', 'flip_rate', 'mean_kl': {'mean', 'std'} (std 0: the direction is deterministic),
+    'per_draw': [evaluate_adversarial_store's dict]}.  The direction costs 3 KB per frame (evaluate_adversarial_store)."""
+    plan = EvalPlan.of(store_or_loader)
+    if plan.labels_d is None:
+        raise ValueError("the split has no labels")
+    eps = [float(v) for v in (default_noise_levels(cfg) if epsilons is None else epsilons)]
+    if eps and eps[0] == 0.0:
+        eps = eps[1:]
+    r = evaluate_adversarial_store(model, plan, eps, steps, alpha, target, use_teacher, precision)
+    res = {"sigmas": list(r["epsilons"]), "epsilons": list(r["epsilons"]), "draws": 1, "per_draw": [r]}
+    for name, key in _CURVE_KEYS:
+        v = [float(lv[key]) for lv in r["levels"]]
+        res[name] = {"mean": v, "std": [0.0] * len(v)}
+    return res
+
+
+def worst_case_report(initial_model, trained_model, store_or_loader, epsilons=None, steps=1, draws=8):
+    """The random and the worst-case response on one axis: {'random': robustness_from_curves of noise_response_curve,
+    'worst_case': robustness_from_curves of adversarial_response_curve}, each for the initial and the trained weights
+    at the same levels (epsilons=None: default_noise_levels)."""
+    return {"random": robustness_from_curves(noise_response_curve(initial_model, store_or_loader, epsilons, draws),
+                                             noise_response_curve(trained_model, store_or_loader, epsilons, draws)),
+            "worst_case": robustness_from_curves(
+                adversarial_response_curve(initial_model, store_or_loader, epsilons, steps),
+                adversarial_response_curve(trained_model, store_or_loader, epsilons, steps))}
