@@ -322,7 +322,10 @@ class DADStep:
             _lib.check(_lib.lib().dad_workspace_bytes(cfg, ctypes.byref(nbytes)), "dad_workspace_bytes")
             need = self._ws_need[key] = int(nbytes.value)
         if self._ws is None or self._ws.numel() < need:
-            # zero-filled once (finite bytes everywhere; the step needs no initialisation)
+            # zero-filled once (finite bytes everywhere; the step needs no initialisation: every byte a step
+            # reads it has written itself, or a named-ahead step's preparation has.  Held by
+            # tests/test_gpu_hidden_state.py: steps from workspaces of 0xFF and 0x01 bytes, and sequences of
+            # geometries through one DADStep, equal the step from this zero-filled one bit for bit)
             old, self._ws = self._ws, torch.zeros(need, dtype=torch.uint8, device=self.device)
             if old is not None and cfg.scl_on:
                 self._ws[:old.numel()].copy_(old)
@@ -612,8 +615,17 @@ class DADStep:
         return [n for n, b in (("nonfinite", _lib.RANGE_NONFINITE), ("pool_timeout", _lib.RANGE_POOL_TIMEOUT))
                 if v & b]
 
+    # outputs() entries a warm-up step writes (its tail is the clean cross-entropy alone, dad_tail with Bn = 0)
+    WARMUP_OUTPUTS = ("e_clean", "z_clean", "ecda_terms", "clip_norm", "clip_coef", "msum", "ecda_on", "grad")
+
     def outputs(self, Bc=None, Bn=None):
-        """Per-step intermediates (device tensors) of the last step, for inspection/tests."""
+        """Per-step intermediates (device tensors) of the last step, for inspection/tests.
+
+        After a warm-up step only the WARMUP_OUTPUTS entries are that step's: the reference's warm-up
+        train_step returns before it touches the noisy batch (I/train.py:402), and so does the step.  Every
+        other entry (the teacher / strong embeddings and logits, score, pred, mask, q, w, tau_before,
+        tau_after) then holds what the last post-warm-up step with this (Bc, Bn) left in the buffers, or
+        their initial zeros; the key set stays the same in both modes."""
         b = self._last
         t = b["tail"]
         nb = (b["emb"].shape[0])

@@ -38,11 +38,12 @@ def _features(rs, n):
     return (np.where(rs.rand(n, 768) < 0.5, -1.0, 1.0) * mag).astype(np.float32)
 
 
-def _layout(rs, groups, filler=None):
+def _layout(rs, groups, filler=None, utterances=None):
     """Store layout of `groups` lists of utterance lengths: (features, sizes, offsets, index per group);
     each utterance starts at an odd row, with 1 or 3 unrelated rows before it and some after the last.
     filler(n) -> [n, 768]: what the unrelated rows hold instead of features (the utterances' rows and
-    the draws from `rs` are the same either way)."""
+    the draws from `rs` are the same either way).  utterances: one [length, 768] array per utterance, in
+    the groups' order, written over the drawn rows of that utterance (tests/hidden_state.py)."""
     sizes, offsets, index, row = [], [], [], 0
     for lens in groups:
         ids = []
@@ -60,6 +61,11 @@ def _layout(rs, groups, filler=None):
         for o, n in zip(offsets, sizes):
             unrelated[o:o + n] = False
         feats[unrelated] = filler(int(unrelated.sum()))
+    if utterances is not None:
+        assert len(utterances) == len(sizes)
+        for o, n, rows in zip(offsets, sizes, utterances):
+            assert rows.shape == (n, 768)
+            feats[o:o + n] = rows
     return feats, np.array(sizes), np.array(offsets), index
 
 
