@@ -1,5 +1,6 @@
 """Synthetic DAD steps whose encoder operands are exactly representable in fp16 AND bf16, with a float64
-reference and an error bound derived from the reference alone (TEST INFRASTRUCTURE; imports oracle/ only).
+reference and an error bound derived from the reference alone (TEST INFRASTRUCTURE; imports oracle/ only, and
+tests/scl_ref.py when a case switches the supervised-contrastive term on).
 
 Why: on random inputs a 16-bit forward flips ReLU' decisions of pre-activations near 0 and each flip moves a
 whole row of dW1 (gpu_harness.close_grad), so no tolerance separates "rounding" from "wrong".  Here the
@@ -48,6 +49,32 @@ Bounds (u = 2^-24, the fp32 unit roundoff; S_x = the reference's sum with every 
   embeddings |e - e_ref| <= (T + 2) u |e_ref|: the pooled terms are exact and non-negative, so only the fp32
               sum and one division round.
   logits      |z - z_ref| <= (T + H + 8) u (|d_ref| |W2|^T + |b2|), d = the dropout-scaled embedding.
+  contrastive term   (cases with TARGET_SCL_WEIGHT > 0 past max(WARMUP_EPOCHS, SCL_START_EPOCH), ConfigView.scl_weight's
+              rule; tests/test_gpu_exact_scl.py.)  The oracle has no such term.  The reference adds the float64
+              definition (scl_ref.scl_autograd, cross-checked against scl_ref.scl_closed_form) on its OWN pre-dropout
+              float64 embeddings: clean rows with yc, strong rows with the oracle's pred, members = every clean row and
+              the strong rows with mask != 0.  w_scl g_u joins each branch's dL/de before the weight-gradient sum, so dW1
+              and db1 move and dW2, db2 do not; S_W1 and S_b1 add |base| and w_scl |g| WITHOUT cancellation between
+              them; the expected total loss is the oracle's plus w_scl x loss.  dad_scl evaluates the term in fp32, and
+              its error is no fraction of S (the term's own gradient cancels), so dW1 and db1 gain an allowance that
+              enters the way the tail term does: through wgrad64_scaled's magnitude sum with, in place of |dL/de|, per
+              element of a member row
+                w_scl (1e-4 max |g| + 4 d),
+              1e-4 max |g| being the project's own bound on dad_scl's gradient (tests/test_gpu_scl.py's TOL in
+              gpu_harness.close's measure) and d its sensitivity to the embeddings it is fed, which are fp32 and may
+              differ from the float64 ones by (T + 2) u |e|.  d is measured on the reference, never on a kernel: the
+              largest change of any element of the float64 g under three seeded sign patterns of e (1 +- (T + 2) u) and
+              under the embeddings of a float32 restatement of the pooling (pool32); 4x is the factor
+              tests/test_gpu_domain_gap.py puts on a measured sensitivity.  Measured 4 d / (1e-4 max |g|): 0.40 at
+              B5T33/Bn7Tn31, 0.50 at B16T64/Bn16Tn64, 0.51 at B12T45/Bn20Tn70, 0.39 at B64T40/Bn64Tn40, 0.26 at
+              B65T33/Bn66Tn31 and 4.2 at L1 (T = 544 / 577: the rows are nearly parallel, 1 / tau = 10 and (T + 2) u =
+              3.4e-5): never below a tenth of the first part, so it stays in.  With no anchor (B1T1/Bn2Tn3: three
+              members of three classes) g = 0, the allowance is 0 and the bounds are the weight-0 step's.  The float32
+              restatement of the whole route sits at most 0.02 of the fp32 bound, and the term dropped, overwriting the
+              ECDA part, or with wrong members, labels, embeddings, normalisation backward, temperature, mean or input
+              lies at least 22x outside the bf16 bound (test_exact_problem_cpu.py asserts 10x and prints each factor).
+              The term's median share of S_W1 is 0.036 - 0.038 with ECDA on at weight 1 (0.027 at B64T40/Bn64Tn40,
+              hence weight 2 there: SCL_WEIGHT) and 0.78 - 0.88 where ECDA is off.
 The forward bounds hold for ALL three precisions: the 16-bit conversion is lossless on these inputs, so a 16-bit
 forward that differs from the fp32 one beyond summation order is a bug.
 
@@ -83,6 +110,12 @@ TAU_RANGE_OPEN = (0.05, 0.3)
 U32 = 2.0 ** -24
 EPS_OP = {"fp32": 0.0, "fp16": 2.0 ** -11, "bf16": 2.0 ** -8}
 TAIL_TOL = 1e-4                # gpu_harness.close_grad's tol_norm
+SCL_TOL = 1e-4                 # tests/test_gpu_scl.py's TOL for dad_scl's gradient, in gpu_harness.close's measure
+SCL_SENS_FACTOR = 4.0          # on a measured sensitivity, as tests/test_gpu_domain_gap.py takes it
+SCL_ON = dict(TARGET_SCL_WEIGHT=1.0, SCL_START_EPOCH=0, SCL_TEMPERATURE=0.1)
+# ... but for B64T40/Bn64Tn40, where weight 1 gives the term a median 0.027 of S_W1 with ECDA on: below the 0.03 the
+# CPU module asks for, so the weight is raised there (0.052)
+SCL_WEIGHT = {"B64T40_Bn64Tn40": 2.0}
 # tests/test_gpu_parity.EDGE (the GPU module asserts they are the same)
 GEOMS = [
     dict(B=1, T=1, Bn=2, Tn=3),
@@ -91,6 +124,9 @@ GEOMS = [
     dict(B=12, T=45, Bn=20, Tn=70, ragged=False),
     dict(B=64, T=40, Bn=64, Tn=40),
 ]
+# Past 64 utterances a side (the general tail, dad_tail_ecda; 131 candidate rows for dad_scl: a third row tile and a
+# second column chunk).  Not one of test_gpu_parity's; tests/test_gpu_exact_scl.py runs it.
+PAST64 = dict(B=65, T=33, Bn=66, Tn=31)
 
 
 SENT0, SENT_N = 640, 128       # the sentinel channels 640 .. 767 of the long problems (long_problem)
@@ -134,6 +170,15 @@ S1_PLUS = dict(LONG["S1"], id="S1plus", B=33, lens_c=LONG["S1"]["lens_c"] + (17,
 
 def geom_id(g):
     return g["id"] if "id" in g else "B%dT%d_Bn%dTn%d" % (g["B"], g["T"], g["Bn"], g["Tn"])
+
+
+def scl_over(geom, ecda=True, weight=None):
+    """The settings of a case with the contrastive term on, beside cfg(): SCL_ON with the geometry's weight (or
+    `weight`), and USE_ECDA=False where asked.  Both the reference (case) and the step under test take them."""
+    over = dict(SCL_ON, TARGET_SCL_WEIGHT=SCL_WEIGHT.get(geom_id(geom), 1.0) if weight is None else float(weight))
+    if not ecda:
+        over["USE_ECDA"] = False
+    return over
 
 
 def q(a, step):
@@ -305,6 +350,83 @@ def _logits64(e, W2, b2, keep, p):
     return d @ W2.T + b2, d, np.abs(d) @ np.abs(W2).T + np.abs(b2)
 
 
+def scl_weight(c, epoch):
+    """The supervised-contrastive term's weight at `epoch` (ConfigView.scl_weight's rule; the oracle's settings have
+    no such keys unless a case adds them)."""
+    if epoch < max(c["WARMUP_EPOCHS"], c.get("SCL_START_EPOCH", 0)):
+        return 0.0
+    return float(c.get("TARGET_SCL_WEIGHT", 0.0))
+
+
+def scl_inputs(inp, r, e_clean, e_strong):
+    """(embeddings [Bc + Bn, H], classes, member flags) of the term: every clean row with its label, then the strong
+    rows with the oracle's pseudo-labels, flagged where the DACP mask lets them in."""
+    emb = np.concatenate([e_clean, e_strong], 0)
+    labels = np.concatenate([np.asarray(inp["yc"], np.int64), np.asarray(r["pred"], np.int64)])
+    member = np.concatenate([np.ones(len(inp["yc"]), np.uint8), (np.asarray(r["mask"]) != 0).astype(np.uint8)])
+    return emb, labels, member
+
+
+def scl_perturbed(emb, T_rows, seed):
+    """`emb` with every element moved to the embedding bound, e (1 +- (T + 2) u), the signs seeded."""
+    sign = np.random.RandomState(seed).choice([-1.0, 1.0], size=emb.shape)
+    return emb * (1.0 + sign * ((np.asarray(T_rows, np.float64) + 2.0) * U32)[:, None])
+
+
+def pool32(x, pad, W1, b1):
+    """The pooled encoder restated in float32: exact pre-activations, a float32 sum over the frames in order and one
+    division."""
+    pre = preact64(x, W1, b1).astype(np.float32)
+    act = (pre > 0) & ~pad[..., None]
+    vlen = np.maximum((~pad).sum(1), 1).astype(np.float32)
+    return np.cumsum(np.where(act, pre, np.float32(0)), axis=1, dtype=np.float32)[:, -1] / vlen[:, None]
+
+
+def _add_scl(ref, inp, st, c, w):
+    """The supervised-contrastive term on top of the rebuilt step `ref` (module docstring, "contrastive term"): the
+    float64 definition on the reference's own pre-dropout embeddings, w dL_scl/de added to each branch's dL/de
+    before the weight-gradient sums, the magnitude sums and the allowance added beside the base's."""
+    import scl_ref
+    W1, b1 = st["student"][:2]
+    tau = c.get("SCL_TEMPERATURE", 0.1)
+    pc, ps = ref["parts"]["clean"], ref["parts"]["strong"]
+    Bc = pc["x"].shape[0]
+    emb, labels, member = scl_inputs(inp, ref["oracle"], ref["e"]["e_clean"], ref["e"]["e_strong"])
+    loss, g = scl_ref.scl_autograd(emb, labels, member, tau)
+    loss_cf, g_cf = scl_ref.scl_closed_form(emb, labels, member, tau)
+    stats = scl_ref.stats(emb, labels, member)
+    gmax = float(np.abs(g).max())
+    # sensitivity to the embeddings' own fp32 error, measured on the reference: the float64 term on embeddings moved
+    # to the embedding bound and on the float32 restatement's
+    T_rows = np.concatenate([np.full(Bc, ref["T"]["e_clean"]), np.full(len(emb) - Bc, ref["T"]["e_strong"])])
+    others = [scl_perturbed(emb, T_rows, s) for s in (0, 1, 2)]
+    others.append(np.concatenate([pool32(pc["x"], inp["mc"], W1, b1), pool32(ps["x"], inp["mn"], W1, b1)], 0).astype(np.float64))
+    moved = max(float(np.abs(scl_ref.scl_autograd(e2, labels, member, tau)[1] - g).max()) for e2 in others)
+    allow = np.zeros(len(emb))
+    allow[scl_ref.members(emb, labels, member)] = w * (SCL_TOL * gmax + SCL_SENS_FACTOR * moved)
+    dW1, db1 = ref["grads"][0].copy(), ref["grads"][1].copy()
+    S1, Sb1 = ref["S"][0].copy(), ref["S"][1].copy()
+    S_term, tail, tail_b1 = np.zeros_like(S1), ref["tail"].copy(), np.zeros_like(Sb1)
+    for p, rows in ((pc, slice(0, Bc)), (ps, slice(Bc, None))):
+        n = np.maximum(p["vlen"], 1.0)[:, None]
+        tW, tS, tb, tSb = wgrad64_scaled(p["x"], p["act"], w * g[rows] / n)
+        aS, aSb = wgrad64_scaled(p["x"], p["act"], allow[rows, None] / n * np.ones((1, g.shape[1])))[1::2]
+        dW1, db1, S1, Sb1, S_term = dW1 + tW, db1 + tb, S1 + tS, Sb1 + tSb, S_term + tS
+        tail, tail_b1 = tail + aS, tail_b1 + aSb
+    with np.errstate(divide="ignore", invalid="ignore"):
+        share = float(np.median((S_term / S1)[S1 > 0])) if stats["V"] else 0.0
+    ref["scl"] = dict(w=w, tau=tau, loss=loss, g=g, loss_closed=loss_cf, g_closed=g_cf, V=stats["V"],
+                      members=stats["members"], anchors=stats["anchors"], allow=allow,
+                      sensitivity=SCL_SENS_FACTOR * moved / (SCL_TOL * gmax) if gmax > 0 else 0.0,
+                      base=dict(clean=pc["g"], strong=ps["g"]), labels=labels, member=member, S_term=S_term, share=share)
+    ref["parts"] = dict(ref["parts"], clean=dict(pc, g=pc["g"] + w * g[:Bc]), strong=dict(ps, g=ps["g"] + w * g[Bc:]))
+    ref["grads"] = [dW1, db1] + ref["grads"][2:]
+    ref["S"] = [S1, Sb1] + ref["S"][2:]
+    ref["tail"], ref["tail_b1"] = tail, tail_b1
+    ref["total_loss"] = ref["oracle"]["total_loss"] + w * loss
+    return ref
+
+
 def reference(inp, st, c, epoch):
     """One DADOracle.step from state `st`, then the float64 rebuild.  Returns a dict:
       oracle   the oracle's own output (losses, mask, fp32 grads, ...)
@@ -312,7 +434,14 @@ def reference(inp, st, c, epoch):
       strong   the strong branch's share (dW1, S_W1) (zeros in the warm-up)
       e, z     float64 embeddings / logits by name (e_clean, ...);  zS: the logit bound's magnitude sum
       T        the padded length behind each e_* / z_* name;  n_rows = Bc Tc + Bn Tn
-      parts    what the gradient was built from (x, act, vlen, g per branch), for the CPU module's mutants"""
+      parts    what the gradient was built from (x, act, vlen, g per branch), for the CPU module's mutants
+    With the supervised-contrastive term on (scl_weight(c, epoch) > 0) the gradients, S, tail and parts include it,
+    and the dict also holds
+      scl      loss, g [Bc + Bn, H] (dL_scl/de, unweighted), w, tau, V, members, anchors [4], loss_closed / g_closed
+               (scl_ref.scl_closed_form beside the autograd), allow [Bc + Bn] (the per-row allowance, weighted),
+               sensitivity (the allowance's second part over its first), base (the branches'
+               dL/de without the term), S_term (the term's part of S_W1) and share (its median share of S_W1)
+      tail_b1  db1's allowance for the term [H];  total_loss: the oracle's plus w x loss"""
     W1, b1, W2, b2 = st["student"]
     orc = dad_oracle.DADOracle(W1, b1, W2, b2, c)
     orc.load_state(st)
@@ -370,8 +499,10 @@ def reference(inp, st, c, epoch):
         dW1, S1, db1, Sb1 = dW1 + strong[0], S1 + strong[1], db1 + strong[2], Sb1 + strong[3]
         dW2, S2 = dW2 + gzs.T @ ds, S2 + np.abs(gzs).T @ np.abs(ds)
         db2, Sb2 = db2 + gzs.sum(0), Sb2 + np.abs(gzs).sum(0)
-    return dict(oracle=r, grads=[dW1, db1, dW2, db2], S=[S1, Sb1, S2, Sb2], tail=tail, strong=strong[:2], e=e, z=z,
-                zS=zS, T=T, n_rows=Bc * Tc + Bn * Tn, parts=parts)
+    ref = dict(oracle=r, grads=[dW1, db1, dW2, db2], S=[S1, Sb1, S2, Sb2], tail=tail, strong=strong[:2], e=e, z=z,
+               zS=zS, T=T, n_rows=Bc * Tc + Bn * Tn, parts=parts)
+    w_scl = scl_weight(c, epoch)
+    return _add_scl(ref, inp, st, c, w_scl) if w_scl > 0 else ref
 
 
 _CASES = {}
@@ -391,7 +522,14 @@ def case(geom, epoch, **cfg_over):
             ragged = g.pop("ragged", True)
             inp = problem(ragged=ragged, **g)
             st = state(tau_range=tau_range(g["Bn"]))
-        _CASES[key] = (inp, st, reference(inp, st, dict(cfg(), **cfg_over), epoch))
+        c = dict(cfg(), **cfg_over)
+        if scl_weight(c, epoch) > 0:
+            # No step reads the noisy batch's labels.  On these problems the teacher's pseudo-label of every
+            # masked-in row IS the true label, so a term fed the labels would pass; the cases with the term on hand
+            # the step labels that differ from the pseudo-label in every such row (test_exact_problem_cpu.py checks
+            # it; the reference does not depend on them).
+            inp = dict(inp, yn=(inp["yn"] + 1) % synth.N_CLS)
+        _CASES[key] = (inp, st, reference(inp, st, c, epoch))
     return _CASES[key]
 
 
@@ -426,8 +564,11 @@ def grad_ratios(grads, ref, precision):
 
 
 def grad_limit(name, precision, ref):
-    """The elementwise bound of gradient tensor `name`: bound() x S, and for dW1 the tail term."""
+    """The elementwise bound of gradient tensor `name`: bound() x S, for dW1 the tail term, and with the contrastive
+    term on its allowance in dW1 (inside ref["tail"]) and db1."""
     lim = bound(name, precision, ref["n_rows"]) * ref["S"][GRAD_NAMES.index(name)]
+    if name == "db1" and "tail_b1" in ref:
+        return lim + ref["tail_b1"]
     return lim + ref["tail"] if name == "dW1" else lim
 
 

@@ -320,3 +320,209 @@ def test_pool_mutants_past_16_slabs_exceed_the_bounds_tenfold(geom):
         r = X.worst(db1 - ref["grads"][1], X.grad_limit("db1", "fp16", ref))
         print("%s: %s: db1 %.0f x its bound" % (X.geom_id(geom), what, r))
         assert r >= 10.0, (what, r)
+
+
+# ---------------------------------------------------------------- the supervised-contrastive term
+# (tests/test_gpu_exact_scl.py's cases: exact_problem's reference with the term, "contrastive term" in its docstring)
+
+def _scl_cases():
+    cases = [(g, ecda, None) for g in X.GEOMS for ecda in (True, False)]
+    cases += [(X.PAST64, True, None), (X.LONG["L1"], True, None), (X.GEOMS[2], True, 8.0)]
+    return cases
+
+
+def _scl_id(c):
+    return X.geom_id(c[0]) + ("" if c[1] else "-noecda") + ("-w%g" % c[2] if c[2] else "")
+
+
+SCL_CASES = pytest.mark.parametrize("case", _scl_cases(), ids=_scl_id)
+
+
+def _scl_case(case):
+    geom, ecda, weight = case
+    return X.case(geom, EPOCH, **X.scl_over(geom, ecda, weight))
+
+
+LOOSEST = "bf16"       # the loosest bound a case is checked under, ECDA on or off: its eps_op is the largest of the three
+
+
+def test_scl_weight_rule_and_the_off_path():
+    c = dict(X.cfg(), **X.SCL_ON)
+    assert [X.scl_weight(c, e) for e in (0, 29, 30, 60)] == [0.0, 0.0, 1.0, 1.0]
+    assert X.scl_weight(dict(c, SCL_START_EPOCH=61), 60) == 0.0 and X.scl_weight(X.cfg(), 60) == 0.0
+    ref = X.case(X.GEOMS[1], EPOCH)[2]
+    assert "scl" not in ref and "tail_b1" not in ref and "total_loss" not in ref
+    # the term moves dW1 and db1 only, and the base it is added to is the step's without it
+    on = _scl_case((X.GEOMS[1], True, None))[2]
+    for i in (2, 3):
+        assert np.array_equal(on["grads"][i], ref["grads"][i]) and np.array_equal(on["S"][i], ref["S"][i])
+    assert np.array_equal(on["scl"]["base"]["clean"], ref["parts"]["clean"]["g"])
+    assert not np.array_equal(on["grads"][0], ref["grads"][0]) and not np.array_equal(on["grads"][1], ref["grads"][1])
+    assert on["total_loss"] == ref["oracle"]["total_loss"] + on["scl"]["loss"]
+
+
+@SCL_CASES
+def test_scl_gates_members_and_the_two_restatements_agree(case):
+    geom = case[0]
+    inp, st, ref = _scl_case(case)
+    s, r = ref["scl"], ref["oracle"]
+    mask = np.asarray(r["mask"])
+    margin = np.abs(np.asarray(r["score"], np.float64) - np.asarray(r["tau_after"], np.float64)[r["pred"]]).min()
+    assert mask.sum() >= 2 and r["consistency_loss"] != 0.0
+    if geom["Bn"] >= 7:
+        assert mask.min() == 0 and mask.max() == 1 and margin >= 0.07, (mask, margin)
+    assert s["members"] == len(inp["yc"]) + int(mask.sum()) and s["V"] == int(np.sum(s["anchors"]))
+    # the noisy labels handed to the step are wrong in every row the mask lets in
+    assert np.all((inp["yn"] != np.asarray(r["pred"]))[mask > 0])
+    gmax = np.abs(s["g"]).max()
+    agree = np.abs(s["g"] - s["g_closed"]).max() / gmax if gmax > 0 else 0.0
+    print("%s: members %d, anchors %s, loss %.6f; autograd against the closed form %.2g of max |g|; the allowance's "
+          "sensitivity part is %.2f of its 1e-4 part" % (_scl_id(case), s["members"], [int(a) for a in s["anchors"]], s["loss"], agree,
+                                                         s["sensitivity"]))
+    assert agree <= 1e-12 and abs(s["loss"] - s["loss_closed"]) <= 1e-12 * max(1.0, abs(s["loss"]))
+    if s["V"] == 0:
+        assert s["loss"] == 0.0 and not np.any(s["g"]) and geom["B"] == 1
+    if geom is X.PAST64:
+        assert len(s["member"]) > 128 and s["members"] > 64 and ref["parts"]["clean"]["x"].shape[0] > 64 and len(mask) > 64
+
+
+@SCL_CASES
+def test_scl_term_is_visible_in_the_weight_gradient(case):
+    ref = _scl_case(case)[2]
+    s = ref["scl"]
+    rest = ref["S"][0] - s["S_term"]
+    print("%s: the term's share of S_W1 %.4f (median over the elements; %.3g x everything else); |w g| %.3f" % (
+        _scl_id(case), s["share"], np.median(s["S_term"][rest > 0] / rest[rest > 0]) if s["V"] else 0.0,
+        s["w"] * np.linalg.norm(s["g"])))
+    if s["V"]:
+        assert s["share"] >= 0.03, s["share"]
+
+
+def _f32_restatement(inp, st, ref):
+    """[dW1, db1] of the step with the term in float32: a float32 pooled encoder, scl_closed_form(dtype=float32) on
+    its embeddings and a float32 weight-gradient sum (the base dL/de: the oracle's, rounded to float32)."""
+    import scl_ref
+    s = ref["scl"]
+    W1, b1 = st["student"][:2]
+    pc, ps = ref["parts"]["clean"], ref["parts"]["strong"]
+    e32 = np.concatenate([X.pool32(pc["x"], inp["mc"], W1, b1), X.pool32(ps["x"], inp["mn"], W1, b1)], 0)
+    assert e32.dtype == np.float32
+    g32 = scl_ref.scl_closed_form(e32, s["labels"], s["member"], s["tau"], dtype=np.float32)[1].astype(np.float32)
+    Bc = pc["x"].shape[0]
+    dW, db = np.zeros(ref["grads"][0].shape, np.float32), np.zeros(ref["grads"][1].shape, np.float32)
+    for p, base, g in ((pc, s["base"]["clean"], g32[:Bc]), (ps, s["base"]["strong"], g32[Bc:])):
+        scale = (base.astype(np.float32) + np.float32(s["w"]) * g) / np.maximum(p["vlen"], 1.0).astype(np.float32)[:, None]
+        for u in range(len(scale)):
+            a = p["act"][u].astype(np.float32).T
+            dW += scale[u][:, None] * (a @ p["x"][u].astype(np.float32))
+            db += scale[u] * a.sum(1)
+    assert dW.dtype == np.float32 and db.dtype == np.float32
+    return dW, db
+
+
+@SCL_CASES
+def test_scl_float32_restatement_lies_inside_every_bound(case):
+    inp, st, ref = _scl_case(case)
+    dW, db = _f32_restatement(inp, st, ref)
+    for prec in ("fp32", "fp16", "bf16"):
+        r = {n: X.worst(g - ref["grads"][i], X.grad_limit(n, prec, ref)) for i, (n, g) in enumerate((("dW1", dW), ("db1", db)))}
+        print("%s: float32 restatement, %s bound: dW1 %.3f db1 %.3f" % (_scl_id(case), prec, r["dW1"], r["db1"]))
+        assert max(r.values()) <= 1.0, (prec, r)
+
+
+def _scl_of_z(z, y, tau):
+    """scl_ref.scl_torch's loss as a function of the unit rows themselves (nothing normalised inside)."""
+    y = torch.as_tensor(np.asarray(y))
+    m = z.shape[0]
+    s = (z @ z.T) / tau
+    eye = torch.eye(m, dtype=torch.bool)
+    lse = torch.logsumexp(s.masked_fill(eye, -float("inf")), dim=1)
+    pos = (y[:, None] == y[None, :]) & ~eye
+    npos = pos.sum(1)
+    anchor = npos >= 1
+    return (-((s - lse[:, None]) * pos).sum(1)[anchor] / npos[anchor]).mean()
+
+
+def _scl_dw1(ref, g, base=None, strong=None):
+    """dW1 in float64: the branches' base dL/de (or `base`) through their own inputs, plus w x the term `g`
+    [Bc + Bn, H]; strong: replacement (x, act) for the TERM's strong rows."""
+    s = ref["scl"]
+    pc, ps = ref["parts"]["clean"], ref["parts"]["strong"]
+    base = s["base"] if base is None else base
+    Bc = pc["x"].shape[0]
+    dw = X.wgrad64(pc["x"], pc["act"], pc["vlen"], base["clean"] + s["w"] * g[:Bc])[0]
+    dw += X.wgrad64(ps["x"], ps["act"], ps["vlen"], base["strong"])[0]
+    tx, tact = (ps["x"], ps["act"]) if strong is None else strong
+    return dw + X.wgrad64(tx, tact, ps["vlen"], s["w"] * g[Bc:])[0]
+
+
+def _scl_controls(case):
+    """(name, wrong dW1) for every way the issue lists of carrying the term wrongly that applies to the case."""
+    import scl_ref
+    geom, ecda, weight = case
+    inp, st, ref = _scl_case(case)
+    s, r = ref["scl"], ref["oracle"]
+    emb, labels, member, tau = np.concatenate([ref["e"]["e_clean"], ref["e"]["e_strong"]], 0), s["labels"], s["member"], s["tau"]
+    Bc = len(inp["yc"])
+    yield "the term dropped", _scl_dw1(ref, np.zeros_like(s["g"]))
+    if ecda and r["ecda_loss"] != 0.0:
+        off = X.case(geom, EPOCH, **X.scl_over(geom, False, weight))[2]["scl"]["base"]
+        m = (member != 0)[:, None]
+        base = dict(clean=np.where(m[:Bc], off["clean"], s["base"]["clean"]), strong=np.where(m[Bc:], off["strong"], s["base"]["strong"]))
+        assert not np.array_equal(base["clean"], s["base"]["clean"])
+        yield "the term overwrites the ECDA part of the flagged rows", _scl_dw1(ref, s["g"], base=base)
+    if not member.all():
+        yield "masked-out strong rows taken as members", _scl_dw1(ref, scl_ref.scl_autograd(emb, labels, np.ones_like(member), tau)[1])
+    true = np.concatenate([inp["yc"], inp["yn"]])
+    yield "the noisy batch's labels in place of the pseudo-labels", _scl_dw1(ref, scl_ref.scl_autograd(emb, true, member, tau)[1])
+    p = X.cfg()["DROPOUT_RATE"]
+    post = emb * np.concatenate([inp["keep1"], inp["keep2"]], 0).astype(np.float64) / (1.0 - p)
+    yield "post-dropout embeddings", _scl_dw1(ref, scl_ref.scl_autograd(post, labels, member, tau)[1])
+    idx = scl_ref.members(emb, labels, member)
+    nrm = np.linalg.norm(emb[idx], axis=1)
+    z = torch.tensor(emb[idx] / nrm[:, None], dtype=torch.float64, requires_grad=True)
+    _scl_of_z(z, labels[idx], tau).backward()
+    g = np.zeros_like(s["g"])
+    g[idx] = z.grad.numpy() / nrm[:, None]
+    yield "the normalisation's backward left out", _scl_dw1(ref, g)
+    yield "tau = 0.07", _scl_dw1(ref, scl_ref.scl_autograd(emb, labels, member, 0.07)[1])
+    if s["V"] != s["members"]:
+        yield "the mean taken over the members", _scl_dw1(ref, s["g"] * s["V"] / s["members"])
+    xw = ref["parts"]["weak_x"]
+    act_w = dad_oracle.encoder_forward(xw, inp["mn"], *st["student"][:2])[1]
+    yield "the strong rows' share sent through the weak input", _scl_dw1(ref, s["g"], strong=(xw, act_w))
+
+
+@SCL_CASES
+def test_scl_wrong_terms_exceed_the_loosest_bound_tenfold(case):
+    geom = case[0]
+    ref = _scl_case(case)[2]
+    assert _ratio(_scl_dw1(ref, ref["scl"]["g"]), ref, "fp32") < 1e-6          # the rebuild itself
+    if ref["scl"]["V"] == 0:
+        return
+    prec = LOOSEST
+    seen = {}
+    lim = X.grad_limit("dW1", prec, ref)
+    for what, dw in _scl_controls(case):
+        # (over the elements that have a bound: the weak input also reaches channels the feature mask zeroes, where
+        # S_W1 = 0 and any value is infinitely far out)
+        seen[what] = X.worst((dw - ref["grads"][0])[lim > 0], lim[lim > 0])
+        print("%s: %s: %.1f x the %s bound" % (_scl_id(case), what, seen[what], prec))
+    least = min(seen, key=seen.get)
+    print("%s: the least factor is %.1f (%s)" % (_scl_id(case), seen[least], least))
+    if X.geom_id(geom) == "B5T33_Bn7Tn31":
+        assert "the mean taken over the members" in seen
+    assert seen[least] >= 10.0, (least, seen[least])
+
+
+def test_scl_weight_8_makes_the_term_and_ecda_of_one_size_in_the_flagged_rows():
+    """Within a factor of 4 of each other, by the norm over the member rows: neither is a rounding of the other in
+    the fp16 weight gradient's per-hidden-unit scale."""
+    geom = X.GEOMS[2]
+    s = _scl_case((geom, True, 8.0))[2]["scl"]
+    off = _scl_case((geom, False, 8.0))[2]["scl"]["base"]
+    m = s["member"] != 0
+    ecda = np.concatenate([s["base"]["clean"] - off["clean"], s["base"]["strong"] - off["strong"]], 0)[m]
+    size = np.linalg.norm(s["w"] * s["g"][m]) / np.linalg.norm(ecda)
+    print("weight 8: |w g_scl| / |ECDA's dL/de| over the member rows %.3f (weight 1: %.3f)" % (size, size / 8.0))
+    assert s["w"] == 8.0 and 0.25 <= size <= 4.0, size

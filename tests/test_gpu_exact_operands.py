@@ -53,11 +53,18 @@ def _dump_measured():
 
 
 def _check(o, step, ref, prec, epoch, what):
-    """Every assertion of one case; the figures are printed and recorded before anything is asserted."""
+    """Every assertion of one case; the figures are printed and recorded before anything is asserted.  A reference
+    with the supervised-contrastive term (ref["scl"], tests/test_gpu_exact_scl.py) also holds the step's scl_loss
+    to 1e-4 of the float64 loss (gpu_harness.close's measure, as tests/test_gpu_scl.py does) and the total to the
+    oracle's plus the weighted term."""
     r = ref["oracle"]
+    scl = ref.get("scl")
+    want = {k: (ref["total_loss"] if scl and k == "total_loss" else r[k]) for k in LOSSES}
     ratios = dict(X.forward_ratios(o, ref))
     ratios.update(X.grad_ratios(o["grads"], ref, prec))
-    loss_err = {k: abs(o[k] - r[k]) / max(1.0, abs(r[k])) for k in LOSSES}
+    loss_err = {k: abs(o[k] - want[k]) / max(1.0, abs(want[k])) for k in LOSSES}
+    if scl:
+        loss_err["scl_loss"] = abs(o["scl_loss"] - scl["loss"]) / max(1e-6, abs(scl["loss"]))
     # for the record only: dW1 against the bound without exact_problem's tail term
     plain = X.worst(o["grads"][0] - ref["grads"][0], X.bound("dW1", prec, ref["n_rows"]) * ref["S"][0])
     print("%s: %s | dW1 without the tail term %.3g | loss rel %s" % (
@@ -66,7 +73,11 @@ def _check(o, step, ref, prec, epoch, what):
     if epoch >= 30:
         np.testing.assert_array_equal(o["mask"], r["mask"], err_msg=what)
     for k in LOSSES:
-        assert loss_err[k] <= TOL, (what, k, o[k], r[k])
+        assert loss_err[k] <= TOL, (what, k, o[k], want[k])
+    if scl:
+        assert loss_err["scl_loss"] < TOL, (what, o["scl_loss"], scl["loss"])
+    else:
+        assert o.get("scl_loss", 0.0) == 0.0, what
     bad = {k: v for k, v in ratios.items() if not v <= 1.0}
     assert not bad, "%s: err / bound above 1: %s" % (what, bad)
     assert int(step.range_flag()) == 0, what

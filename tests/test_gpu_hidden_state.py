@@ -9,8 +9,9 @@ collects (losses, outputs(), parameters, Adam moments, DACP state), DADStep.grad
   1  a dense step from a workspace of 0xFF or of 0x01 bytes is the step from the zero-filled one, and the steps on
      the problems' own draws (fp32, and fp16 / bf16 with explicit draws) also meet every assertion of
      test_gpu_exact_operands.test_step_on_exact_operands (its _check is called): held to float64, not only to
-     themselves.  The counter units cannot be: their draws are not on exact_problem's grid, and the oracle has no
-     supervised-contrastive term, so the SCL cases are compared bit for bit only.
+     themselves.  The counter units cannot be: their draws are not on exact_problem's grid.  The SCL units on the
+     problems' own draws go through the same check against exact_problem's reference WITH the supervised-contrastive
+     term (tests/test_gpu_exact_scl.py); the SCL units on counter draws are compared bit for bit only.
   2  ten steps over G0 .. G4 at both epochs through one DADStep, the seeded state reloaded and adam_step /
      global_step pinned before each: every step is that step alone on a new DADStep.  Once as is, once with the
      whole workspace 0xFF between steps.  The buffer's size per step is hidden_state.sequence_trace's.
@@ -158,11 +159,16 @@ def _snap(step, losses, g, epoch):
 _SOLO = {}
 
 
+def _case(gi, epoch, scl=False):
+    """exact_problem's (inputs, state, reference); with `scl`, the reference with the term (H.SCL's settings)."""
+    return X.case(H.geom(gi), epoch, **(H.SCL if scl else {}))
+
+
 def _solo(unit, mode, gi, epoch, gstep=0, scl=False):
     """The step alone on a new DADStep from the zero-filled workspace (computed once, never changed)."""
     key = (unit, mode, gi, epoch, gstep, scl)
     if key not in _SOLO:
-        inp, st, _ = X.case(H.geom(gi), epoch)
+        inp, st, _ = _case(gi, epoch, scl)
         step = _make(unit, st, scl, gstep=gstep)
         losses = _go(step, unit, _batch(inp, unit, mode), epoch)
         _SOLO[key] = _snap(step, losses, H.geom(gi), epoch)
@@ -181,7 +187,8 @@ def _part1():
                     both = unit in H.UNITS and mode != "store-16"
                     for byte in (H.PATTERNS if both else [H.PATTERNS[(gi + epoch // 60 + (prec == "bf16")) % 2]]):
                         cases.append((unit, mode, gi, epoch, byte, False))
-    for unit, byte in (("fp32-explicit", 0xFF), ("fp16-counter", 0x01), ("bf16-counter", 0xFF)):
+    for unit, byte in (("fp32-explicit", 0xFF), ("fp16-counter", 0x01), ("bf16-counter", 0xFF),
+                       ("fp16-explicit", 0xFF), ("bf16-explicit", 0x01)):
         cases.append((unit, "padded", 3, 60, byte, True))
     return cases
 
@@ -197,7 +204,7 @@ def test_dense_step_from_a_poisoned_workspace(case, monkeypatch):
     want = _solo(unit, mode, gi, epoch, scl=scl)
     if mode != "padded":
         S._no_materialize(monkeypatch)
-    inp, st, ref = X.case(g, epoch)
+    inp, st, ref = _case(gi, epoch, scl)
     step = _make(unit, st, scl)
     batch = _batch(inp, unit, mode)
     draws = batch[2] if H.ALL_UNITS[unit][1] == "explicit" else None
@@ -209,8 +216,10 @@ def test_dense_step_from_a_poisoned_workspace(case, monkeypatch):
     assert step._ws is ws
     got = _snap(step, losses, g, epoch)
     S._assert_same([got], [want])
-    if H.ALL_UNITS[unit][1] == "explicit" and not scl:
-        # the problem's own draws: test_step_on_exact_operands' assertions for this geometry and precision
+    if H.ALL_UNITS[unit][1] == "explicit":
+        # the problem's own draws: test_step_on_exact_operands' assertions for this geometry and precision (with the
+        # term: test_gpu_exact_scl's, the same function on the reference that holds the term)
+        assert ("scl" in ref) == (scl and epoch >= 30)
         o = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else v) for k, v in step.outputs(g["B"], g["Bn"]).items()}
         o.update({k: float(v) for k, v in losses.items()})
         o["grads"] = gh.unflat(o["grad"])

@@ -5,7 +5,9 @@ oracle's gradient plus the term's float64 autograd, a captured graph and prepara
 Bounds.  Loss and gradient of dad_scl: the project's 1e-4 (gpu_harness.close: max-abs over max |ref|); the same
 formulas in float32 on the CPU stay below 1e-5 on these inputs (tests/test_scl_ref_cpu.py), so a miss means a wrong
 term or a wrong order of summation.  The step's dW1 / db1: gpu_harness.close_grad's bounds in fp32; in fp16 the
-gradient bound of tests/test_gpu_16bit.py (direction cosine > 0.99 when the discrete DACP mask agrees)."""
+gradient bound of tests/test_gpu_16bit.py (direction cosine > 0.99 when the discrete DACP mask agrees).  Every element
+of the step's dW1 and db1 with the term on is held to a float64 reference, in fp32, fp16 and bf16, by
+tests/test_gpu_exact_scl.py."""
 import ctypes
 import functools
 
