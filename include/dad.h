@@ -782,6 +782,89 @@ size_t dad_input_grad_workspace_bytes(int64_t n, int64_t slabs, int precision);
  * [0, n * 2^26]; DAD_E_UNSUPPORTED: DAD_PREC_BF16. */
 int dad_input_grad(const dad_input_grad_args* args, void* workspace, void* stream);
 
+/* --- attributions of a split: exact integrated gradients, store-fed (csrc/attribution.hip) ----
+ * dad_input_grad gives the LOCAL gradient.  In a ReLU network that is not an attribution: it sums to nothing, and
+ * gradient x input reads the wrong side of every unit that switches between the baseline and the input.  Integrated
+ * gradients (Sundararajan et al. 2017) along the straight path x' -> x_t sums to the logit difference against the
+ * baseline, and for this network it needs no path sampling: the pre-activation is affine in the path parameter, so
+ * the path integral of ReLU' is an interval length with a closed form.
+ *
+ * Definition.  For utterance u with len frames x_t, a baseline row x' (768 floats, one per call, zeros when NULL)
+ * and the caller's logit cotangent dz_u[4], HELD FIXED along the path (the attributed quantity is F = dz_u . z, e.g.
+ * one logit or a margin; a cotangent that changes along the path, such as a log-probability's, needs quadrature and
+ * is out of scope):
+ *   p0_j   = W1[j] . x' + b1[j]                     (per call, 256 values)
+ *   a_tj   = W1[j] . (x_t - x'),   p1_tj = p0_j + a_tj
+ *   l_tj   = |{alpha in [0, 1] : p0_j + alpha a_tj > 0}|
+ *          = 1                      p0 > 0,  p1 > 0
+ *          = 0                      p0 <= 0, p1 <= 0
+ *          = p1 / (p1 - p0)         p0 <= 0 < p1
+ *          = p0 / (p0 - p1)         p1 <= 0 < p0
+ *   g_u    = W2^T dz_u / max(len, 1)                (dad_input_grad's g_u, the same order of operations)
+ *   attr_t[d]      = (x_t[d] - x'[d]) sum_j l_tj g_u[j] W1[j][d]
+ *   frame_attr_t   = sum_j g_u[j] (ReLU(p1_tj) - ReLU(p0_j))        ( = sum_d attr_t[d] in exact arithmetic )
+ *   chan_attr_u[d] = sum_t attr_t[d],     utt_total_u = sum_t frame_attr_t
+ * l_tj a_tj = ReLU(p1_tj) - ReLU(p0_j) in all four cases, hence sum_d attr_t[d] = frame_attr_t, hence completeness:
+ * utt_total_u = dz_u . (z(x) - z(x')) with z(x') = W2 ReLU(p0) + b2.
+ *
+ * Arithmetic.  a = W1 x comes from the stored rows in place; W1 x' (a prologue launch, one wave per hidden unit,
+ * a fixed order) is subtracted in fp32 behind the GEMM, p1 = p0 + (W1 x - W1 x').  frame_attr is one fma per hidden
+ * unit in a fixed order and needs no second GEMM: with attr == NULL and chan_attr == NULL (frame-only mode) the call
+ * costs one forward pass.  Otherwise the data-gradient GEMM runs on the float coefficients l_tj g_u[j], which stay in
+ * registers between the two GEMMs.  DAD_PREC_FP32: exact-f32 MFMA for both.  DAD_PREC_FP16: the rows, W1 and (for
+ * p0 and W1 x') the baseline are rounded to fp16, fp32 accumulation; the coefficient l_tj (c_u s_u[j]) is formed in
+ * fp32 and rounded once to fp16 with dad_input_grad's power of two c_u, and 1 / c_u and 1 / max(len, 1) are applied in
+ * fp32 after the GEMM (l <= 1, so no coefficient overflows); the factor x_t[d] - x'[d] is the fp32 difference of the
+ * widened stored value and the unrounded baseline in both precisions.
+ *
+ * Layout.  attr is float [32 * slabs][768] and frame_attr float [32 * slabs] in dad_eval_noise's explicit layout;
+ * chan_attr is [n][768] (slab partials in the workspace, then a per-utterance sum in slab order) and utt_total [n]
+ * (a fixed order).  Every output but counts is optional.  Rows past an utterance's length are written 0, so no
+ * buffer needs initialising; a length-0 utterance owns no slab and gets utt_total 0 and a zero chan_attr row.  An
+ * attr element that is not finite is written 0 (and enters chan_attr as 0) and is counted.
+ *
+ * Bit identities.  baseline == NULL equals a baseline of zeros; frame_attr and utt_total are the same bits in
+ * frame-only and full mode; the result of an utterance depends on neither the order of the utterances nor the
+ * slab-to-workgroup assignment; two calls on the same inputs write the same bits (integer atomics only). */
+#define DAD_AT_FRAMES 0         /* frames processed (the sum of lens) */
+#define DAD_AT_NONFINITE 1      /* attr elements, over those frames, that were not finite (written 0); 0 in frame-only mode */
+#define DAD_AT_CROSS 2          /* (t, j) pairs, over those frames, whose path crosses zero (0 < l < 1 by case) */
+#define DAD_AT_ONE 3            /* (t, j) pairs with l = 1 */
+#define DAD_AT_COUNTS 4         /* int64 slots of the counts block */
+/* Rows as dad_eval_args (store, rows, lens, slab_off, slabs).  One network per call.  Enqueue only, no allocation,
+ * no device read on the host; the call itself zeroes counts. */
+typedef struct dad_attribution_args {
+  const void* store;            /* [frames][768], dtype store_dtype */
+  const int64_t* rows;          /* [n] store row of frame 0 */
+  const int32_t* lens;          /* [n] frames */
+  const int32_t* slab_off;      /* [n + 1] exclusive prefix of ceil(lens / 32) */
+  const float* params;          /* [DAD_NPARAM] flat [W1|b1|W2|b2] */
+  const float* dz;              /* [n][4] logit cotangents, required */
+  const float* baseline;        /* [768] or NULL: zeros */
+  float* attr;                  /* [32 * slabs][768] */
+  float* frame_attr;            /* [32 * slabs] */
+  float* chan_attr;             /* [n][768] */
+  float* utt_total;             /* [n] */
+  int64_t* counts;              /* [DAD_AT_COUNTS], required */
+  int64_t n;                    /* utterances, >= 1 */
+  int64_t slabs;                /* slab_off[n] */
+  int32_t store_dtype;          /* DAD_STORE_* */
+  int32_t precision;            /* DAD_PREC_FP32 or DAD_PREC_FP16 */
+} dad_attribution_args;
+/* workspace bytes that hold for every mode: p0, W1 x', x', the slab totals, the slab channel partials
+ * (slabs * 3 KB) and in DAD_PREC_FP16 the two fp16 copies of W1 (0 for unsupported sizes); no initialisation needed */
+size_t dad_attribution_workspace_bytes(int64_t n, int64_t slabs, int precision);
+/* Checked on the host before anything is launched.  DAD_E_ARG: args, workspace or a required pointer is NULL, or an
+ * unknown dtype / precision; DAD_E_SHAPE: n < 1 or slabs outside [0, n * 2^26]; DAD_E_UNSUPPORTED: DAD_PREC_BF16. */
+int dad_attribution(const dad_attribution_args* args, void* workspace, void* stream);
+/* Host-only: what dad_attribution would do with args (the same checks and codes; no workspace needed). */
+#define DAD_AT_PLAN_MODE 0      /* 0: frame-only (one GEMM), 1: full (attr or chan_attr given: two GEMMs) */
+#define DAD_AT_PLAN_BYTES 1     /* the prefix of the workspace this call touches */
+#define DAD_AT_PLAN_LAUNCHES 2  /* kernel launches */
+#define DAD_AT_PLAN_KERNEL 3    /* the slab kernel's instance: 4 * store_dtype + 2 * (FP16) + (full) */
+#define DAD_AT_PLAN_SLOTS 4
+int dad_attribution_plan(const dad_attribution_args* args, int64_t* out);
+
 /* --- class separation of a split's embeddings (csrc/cluster.hip) -------------------------
  * calculate_cluster_metrics (I/iemocap_plot_tsne.py:390-398): scikit-learn's silhouette_score and
  * calinski_harabasz_score of emb [n][256] (dad_eval_split's emb / t_emb) under labels [n], whose

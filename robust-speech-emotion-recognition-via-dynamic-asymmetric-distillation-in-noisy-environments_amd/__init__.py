@@ -29,6 +29,8 @@ from .evaluate import (enqueue_eval_noise, evaluate_noise_store, noise_draws, no
                        robustness_report)
 from .evaluate import (adversarial_response_curve, enqueue_input_grad, evaluate_adversarial_store, input_gradients,
                        worst_case_report)
+from .evaluate import (attribution_plan, enqueue_attribution, integrated_gradients, saliency_from_attributions,
+                       saliency_report)
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
            "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "SupervisedContrastiveLoss", "TrainingTrace",
@@ -41,6 +43,8 @@ __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "D
            "noise_draws", "enqueue_eval_noise", "evaluate_noise_store", "noise_response_curve", "robustness_report",
            "enqueue_input_grad", "input_gradients", "evaluate_adversarial_store", "adversarial_response_curve",
            "worst_case_report",
+           "enqueue_attribution", "attribution_plan", "integrated_gradients", "saliency_report",
+           "saliency_from_attributions",
            "build", "lib"]
 
 

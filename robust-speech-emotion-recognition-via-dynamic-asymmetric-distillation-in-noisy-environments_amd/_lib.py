@@ -89,6 +89,10 @@ EN_SUM_SCORE, EN_SUM_DRIFT, EN_SUM_KL, EN_SUMS = 0, 8, 16, 24
 # dad_input_grad (dad.h DAD_IG_*): the int64 slots of the counts block
 IG_FRAMES, IG_NONFINITE, IG_ZERO, IG_COUNTS = 0, 1, 2, 4
 
+# dad_attribution (dad.h DAD_AT_*): the int64 slots of the counts block, and dad_attribution_plan's slots
+AT_FRAMES, AT_NONFINITE, AT_CROSS, AT_ONE, AT_COUNTS = 0, 1, 2, 3, 4
+AT_PLAN_MODE, AT_PLAN_BYTES, AT_PLAN_LAUNCHES, AT_PLAN_KERNEL, AT_PLAN_SLOTS = 0, 1, 2, 3, 4
+
 
 class DadConfig(ctypes.Structure):
     _fields_ = [
@@ -190,6 +194,14 @@ class DadInputGradArgs(ctypes.Structure):
                    ("store_dtype", ctypes.c_int32), ("precision", ctypes.c_int32)])
 
 
+class DadAttributionArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_void_p) for n in
+                 ("store", "rows", "lens", "slab_off", "params", "dz", "baseline", "attr", "frame_attr", "chan_attr",
+                  "utt_total", "counts")]
+                + [("n", ctypes.c_int64), ("slabs", ctypes.c_int64), ("store_dtype", ctypes.c_int32),
+                   ("precision", ctypes.c_int32)])
+
+
 class DadTsneArgs(ctypes.Structure):
     _fields_ = [("max_iter", ctypes.c_int32), ("n_iter_without_progress", ctypes.c_int32),
                 ("early_exaggeration", ctypes.c_double), ("learning_rate", ctypes.c_double),
@@ -275,6 +287,9 @@ EXPORTS = {
     "dad_eval_noise_draws": (ctypes.c_int, [ctypes.POINTER(DadNoiseArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "dad_input_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "dad_input_grad": (ctypes.c_int, [ctypes.POINTER(DadInputGradArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_attribution_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "dad_attribution": (ctypes.c_int, [ctypes.POINTER(DadAttributionArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_attribution_plan": (ctypes.c_int, [ctypes.POINTER(DadAttributionArgs), ctypes.POINTER(ctypes.c_int64)]),
     "dad_augment": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -369,7 +384,8 @@ OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_step_plan_kernels", "dad_trace_
                     "dad_scl_workspace_bytes", "dad_scl_plan", "dad_scl", "dad_scl_chunked",
                     "dad_eval_windows_workspace_bytes", "dad_eval_windows",
                     "dad_eval_noise_workspace_bytes", "dad_eval_noise", "dad_eval_noise_draws",
-                    "dad_input_grad_workspace_bytes", "dad_input_grad")
+                    "dad_input_grad_workspace_bytes", "dad_input_grad",
+                    "dad_attribution_workspace_bytes", "dad_attribution", "dad_attribution_plan")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

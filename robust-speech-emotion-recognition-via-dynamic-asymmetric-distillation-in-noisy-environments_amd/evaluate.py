@@ -55,7 +55,15 @@ csrc/input_grad.hip):
   enqueue_input_grad, input_gradients, evaluate_adversarial_store, adversarial_response_curve, worst_case_report
                       not in the reference (its inputs do not require grad): autograd of SSRLModel.predict with respect
                       to x, FGSM (Goodfellow et al. 2015) and PGD (Madry et al. 2018)
+
+and why a split is classified as it is, exact integrated gradients of the stored rows (dad_attribution,
+csrc/attribution.hip):
+
+  enqueue_attribution, attribution_plan, integrated_gradients, saliency_report, saliency_from_attributions
+                      not in the reference: integrated gradients (Sundararajan et al. 2017) of a fixed logit
+                      cotangent along the straight path from a baseline frame, in closed form
 """
+import ctypes
 import warnings
 
 import numpy as np
@@ -1972,3 +1980,276 @@ def worst_case_report(initial_model, trained_model, store_or_loader, epsilons=No
             "worst_case": robustness_from_curves(
                 adversarial_response_curve(initial_model, store_or_loader, epsilons, steps),
                 adversarial_response_curve(trained_model, store_or_loader, epsilons, steps))}
+
+
+# ---- why a split is classified as it is: exact integrated gradients (dad_attribution, csrc/attribution.hip) -------
+_AT_OUTPUTS = ("attr", "frame_attr", "chan_attr", "utt_total")
+_AT_TARGETS = ("pred", "label", "margin")
+
+
+def _at_check_outputs(outputs):
+    outputs = tuple(outputs)
+    for name in outputs:
+        if name not in _AT_OUTPUTS:
+            raise ValueError("unknown output %r (one of %s)" % (name, ", ".join(_AT_OUTPUTS)))
+    return outputs
+
+
+def _at_check_target(target):
+    if isinstance(target, str):
+        if target not in _AT_TARGETS:
+            raise ValueError("unknown target %r (one of %s, or a class index)" % (target, ", ".join(_AT_TARGETS)))
+        return target
+    if isinstance(target, bool) or not isinstance(target, (int, np.integer)) or not 0 <= int(target) < 4:
+        raise ValueError("a target class index must be an integer in [0, 4), got %r" % (target,))
+    return int(target)
+
+
+def _at_check_baseline(baseline, allow_mean):
+    """None, 'mean' (integrated_gradients only) or a contiguous float32 [768] tensor; the device is checked against
+    the plan's by the caller."""
+    if baseline is None or (allow_mean and isinstance(baseline, str) and baseline == "mean"):
+        return baseline
+    if (not isinstance(baseline, torch.Tensor) or baseline.dtype != torch.float32 or tuple(baseline.shape) != (768,)
+            or not baseline.is_contiguous()):
+        raise ValueError("baseline must be None%s or a contiguous float32 [768] tensor, got %s"
+                         % (", 'mean'" if allow_mean else "",
+                            "%s %s" % (baseline.dtype, tuple(baseline.shape)) if isinstance(baseline, torch.Tensor)
+                            else repr(baseline)))
+    return baseline
+
+
+def _at_buffers(plan):
+    b = plan._noise.get("attribution")
+    if b is None:
+        b = {"counts_d": torch.zeros(_lib.AT_COUNTS, dtype=torch.int64, device=plan.device),
+             "counts_h": torch.zeros(_lib.AT_COUNTS, dtype=torch.int64).pin_memory(), "ws": None}
+        plan._noise["attribution"] = b
+    return b
+
+
+def _at_args(model, plan, dz, baseline, use_teacher, prec, out, counts):
+    store = plan.store
+    a = _lib.DadAttributionArgs()
+    a.store = store.feats.data_ptr()
+    a.rows, a.lens, a.slab_off = plan.rows_d.data_ptr(), plan.lens_d.data_ptr(), plan.slab_off_d.data_ptr()
+    a.params = (model.teacher_flat if use_teacher else model.student_flat).data_ptr()
+    a.dz = dz.data_ptr()
+    a.baseline = None if baseline is None else baseline.data_ptr()
+    for name in _AT_OUTPUTS:
+        setattr(a, name, (out[name].data_ptr() or None) if name in out else None)
+    a.counts = counts.data_ptr()
+    a.n, a.slabs = plan.n, plan.slabs
+    a.store_dtype = STORE_DTYPES[store.feats.dtype]
+    a.precision = prec
+    return a
+
+
+def _at_plan(a):
+    slots = (ctypes.c_int64 * _lib.AT_PLAN_SLOTS)()
+    _lib.check(_lib.require("dad_attribution_plan", "the attributions")(a, slots), "dad_attribution_plan")
+    return {"mode": "full" if slots[_lib.AT_PLAN_MODE] else "frame_only",
+            "workspace_bytes": int(slots[_lib.AT_PLAN_BYTES]), "launches": int(slots[_lib.AT_PLAN_LAUNCHES]),
+            "kernel": int(slots[_lib.AT_PLAN_KERNEL])}
+
+
+def enqueue_attribution(model, plan, dz, baseline=None, use_teacher=False, precision="fp32", outputs=("frame_attr",),
+                        _counts=None, _plan_only=False, _out=None):
+    """dad_attribution on the current stream, enqueue only (no copy, no synchronisation; graph-capturable): exact
+    integrated gradients of sum_u dz_u . z_u along the straight path from the baseline row (None: zeros, or a float32
+    [768] device tensor) to every stored frame, with the logit cotangents dz [n, 4] (float32, on the device) held
+    fixed along the path.  outputs: 'attr' [32 * slabs, 768] and 'frame_attr' [32 * slabs] in noise_draws' layout
+    (frame t of utterance i in row 32 * slab_off[i] + t; rows past an utterance's length are 0), 'chan_attr'
+    [n, 768], 'utt_total' [n].  Without 'attr' and 'chan_attr' the call runs one GEMM (frame-only mode), else two.
+    'attr' is float32, 3 KB per frame (about 4 GB for 5,531 utterances).  The DAD_AT_* counts land in the plan's
+    block.  Returns the {name: device tensor} of the requested outputs."""
+    prec = _PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    outputs = _at_check_outputs(outputs)
+    _at_check_baseline(baseline, False)
+    dev = plan.device
+    if model.student_flat.device != dev:
+        raise RuntimeError("model on %s, store on %s" % (model.student_flat.device, dev))
+    if baseline is not None and baseline.device != dev:
+        raise ValueError("baseline on %s, store on %s" % (baseline.device, dev))
+    if (not isinstance(dz, torch.Tensor) or dz.dtype != torch.float32 or dz.device != dev or not dz.is_contiguous()
+            or tuple(dz.shape) != (plan.n, 4)):
+        raise ValueError("dz must be a contiguous float32 [%d, 4] tensor on %s" % (plan.n, dev))
+    shapes = {"attr": (32 * plan.slabs, 768), "frame_attr": (32 * plan.slabs,), "chan_attr": (plan.n, 768),
+              "utt_total": (plan.n,)}
+    out = {}
+    for name in outputs:
+        t = None if _out is None else _out.get(name)
+        if t is None and _plan_only:
+            out[name] = plan.lens_d          # any non-NULL device pointer: the host plan dereferences none
+            continue
+        if t is None:
+            t = torch.empty(shapes[name], dtype=torch.float32, device=dev)
+        elif t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shapes[name]:
+            raise ValueError("%s must be a contiguous float32 %s tensor on %s" % (name, list(shapes[name]), dev))
+        out[name] = t
+    fn = _lib.require("dad_attribution", "the attributions")
+    b = _at_buffers(plan)
+    a = _at_args(model, plan, dz, baseline, use_teacher, prec, out, b["counts_d"] if _counts is None else _counts)
+    p = _at_plan(a)
+    if _plan_only:
+        return p
+    if b["ws"] is None or b["ws"].numel() < p["workspace_bytes"]:
+        b["ws"] = torch.empty(max(p["workspace_bytes"], 1), dtype=torch.uint8, device=dev)
+    _lib.check(fn(a, _lib.ptr(b["ws"]), torch.cuda.current_stream(dev).cuda_stream), "dad_attribution")
+    return out
+
+
+def attribution_plan(model, plan, dz, baseline=None, use_teacher=False, precision="fp32", outputs=("frame_attr",)):
+    """What enqueue_attribution would launch for these arguments, from the library's host plan (nothing is enqueued):
+    {'mode': 'frame_only' | 'full', 'workspace_bytes' (the part of the workspace the call touches), 'launches',
+    'kernel' (the slab kernel's instance)}."""
+    return enqueue_attribution(model, plan, dz, baseline, use_teacher, precision, outputs, _plan_only=True)
+
+
+def _read_at_counts(plan):
+    b = _at_buffers(plan)
+    b["counts_h"].copy_(b["counts_d"], non_blocking=True)
+    torch.cuda.current_stream(plan.device).synchronize()
+    c = b["counts_h"].numpy().copy()
+    if c[_lib.AT_NONFINITE] > 0:
+        raise _lib.DadError("dad_attribution: %d attribution element(s) are not finite (fp16: an operand beyond "
+                            "+-65504; any precision: non-finite features, baseline or cotangents)"
+                            % c[_lib.AT_NONFINITE])
+    return {"frames": int(c[_lib.AT_FRAMES]), "n_nonfinite": int(c[_lib.AT_NONFINITE]),
+            "n_crossing": int(c[_lib.AT_CROSS]), "n_lambda_one": int(c[_lib.AT_ONE])}
+
+
+def _mean_frame(plan):
+    """The split's mean frame [768] float32, on the device (float64 sums over the utterances' rows, in chunks)."""
+    store, dev = plan.store, plan.device
+    sizes = np.asarray(store.sizes, np.int64)
+    offsets = np.asarray(store.offsets, np.int64)
+    total = torch.zeros(768, dtype=torch.float64, device=dev)
+    if int(sizes.sum()) == int(store.feats.shape[0]):
+        for r in range(0, int(store.feats.shape[0]), 1 << 16):
+            total += store.feats[r:r + (1 << 16)].sum(0, dtype=torch.float64)
+    else:
+        for o, L in zip(offsets, sizes):
+            if L:
+                total += store.feats[int(o):int(o + L)].sum(0, dtype=torch.float64)
+    return (total / max(int(sizes.sum()), 1)).to(torch.float32).contiguous()
+
+
+def _at_cotangent(plan, z, pred, target):
+    """(target class [n] int64, dz [n, 4] float32) of `target` (integrated_gradients)."""
+    pred = pred.to(torch.int64)
+    if target == "label":
+        if plan.labels_d is None:
+            raise ValueError("the split has no labels: target='label' needs them (or use target='pred')")
+        lab = plan.labels_d.to(torch.int64)
+        tgt = torch.where((lab >= 0) & (lab < 4), lab, pred)
+    elif isinstance(target, int):
+        tgt = torch.full_like(pred, target)
+    else:
+        tgt = pred
+    dz = torch.nn.functional.one_hot(tgt, 4).to(torch.float32)
+    if target == "margin":
+        other = z.masked_fill(dz.bool(), float("-inf")).argmax(1)
+        dz = dz - torch.nn.functional.one_hot(other, 4).to(torch.float32)
+    return tgt, dz.contiguous()
+
+
+def integrated_gradients(model, store_or_loader, target="pred", baseline=None, use_teacher=False, precision="fp32",
+                         outputs=("frame_attr", "chan_attr")):
+    """Exact integrated gradients (Sundararajan et al. 2017) of every utterance of a split: which frames and which
+    of the 768 channels carry F = dz . z, against a baseline frame.  target: 'pred' (the predicted class's logit),
+    'label' (the label's where it lies in [0, 4), the prediction's otherwise), 'margin' (the predicted logit minus
+    the runner-up: dz = e_c - e_c') or a class index; the cotangent is held fixed along the path, so log-probability
+    or cross-entropy targets are out of scope.  baseline: None (zeros), 'mean' (the split's mean frame, computed on
+    the device) or a float32 [768] device tensor.  One dad_eval_split for the logits, one dad_attribution.
+
+    Returns the requested device tensors (enqueue_attribution's) plus 'utt_total' [n], 'target' [n], 'dz' [n, 4],
+    'baseline' (None or the tensor used), 'completeness_gap' [n] float64 = utt_total - dz . (z(x) - z(x')) with
+    z(x') = W2 ReLU(W1 x' + b1) + b2 in float64 on the device (0 for an utterance without frames), and the counts
+    'frames', 'n_nonfinite', 'n_crossing', 'n_lambda_one'.  Raises DadError on a non-finite attribution element."""
+    target = _at_check_target(target)
+    outputs = _at_check_outputs(outputs)
+    _at_check_baseline(baseline, True)
+    model.eval()
+    plan = EvalPlan.of(store_or_loader)
+    lname, pname = ("t_logits", "t_pred") if use_teacher else ("logits", "pred")
+    ev = enqueue_eval_split(model, plan, use_teacher, True, precision, (lname, pname))
+    tgt, dz = _at_cotangent(plan, ev[lname], ev[pname], target)
+    if isinstance(baseline, str):
+        baseline = _mean_frame(plan)
+    want = tuple(dict.fromkeys(outputs + ("utt_total",)))
+    out = enqueue_attribution(model, plan, dz, baseline, use_teacher, precision, want)
+    flat = (model.teacher_flat if use_teacher else model.student_flat).detach().to(torch.float64)
+    W1, b1 = flat[:256 * 768].view(256, 768), flat[256 * 768:256 * 769]
+    W2, b2 = flat[256 * 769:256 * 773].view(4, 256), flat[256 * 773:256 * 773 + 4]
+    p0 = b1 if baseline is None else W1 @ baseline.to(torch.float64) + b1
+    z0 = W2 @ torch.relu(p0) + b2
+    gap = out["utt_total"].to(torch.float64) - (dz.to(torch.float64) * (ev[lname].to(torch.float64) - z0)).sum(1)
+    gap = torch.where(plan.lens_d > 0, gap, torch.zeros_like(gap))
+    res = _read_at_counts(plan)
+    res.update(out)
+    res.update(target=tgt, dz=dz, baseline=baseline, completeness_gap=gap)
+    return res
+
+
+def _saliency_of(model, split, target, baseline):
+    """One model on one split (saliency_report): host summaries of integrated_gradients."""
+    plan = EvalPlan.of(split)
+    r = integrated_gradients(model, plan, target, baseline, outputs=("frame_attr", "chan_attr"))
+    chan = r["chan_attr"].cpu().numpy().astype(np.float64)
+    tgt = r["target"].cpu().numpy()
+    fa = np.abs(r["frame_attr"].cpu().numpy().astype(np.float64))
+    _, lens, slab_off = plan_host(plan.store.sizes, plan.store.offsets)
+    profile, count = np.zeros((4, 768)), np.zeros(4, np.int64)
+    np.add.at(profile, tgt, chan)
+    np.add.at(count, tgt, 1)
+    profile /= np.maximum(count, 1)[:, None]
+    shares = []
+    for i, L in enumerate(lens):
+        v = np.sort(fa[32 * int(slab_off[i]):32 * int(slab_off[i]) + int(L)])[::-1]
+        if L > 0 and v.sum() > 0:
+            shares.append((int(np.searchsorted(np.cumsum(v), 0.5 * v.sum())) + 1) / float(L))
+    return {"class_profile": profile, "class_count": count.tolist(),
+            "temporal_concentration": float(np.mean(shares)) if shares else float("nan"),
+            "max_completeness_gap": float(r["completeness_gap"].abs().max().item()),
+            "n_crossing": r["n_crossing"], "frames": r["frames"], "_chan": chan, "_lens": np.asarray(lens)}
+
+
+def _row_cosine(a, b):
+    den = np.linalg.norm(a, axis=1) * np.linalg.norm(b, axis=1)
+    ok = den > 0
+    return float(((a[ok] * b[ok]).sum(1) / den[ok]).mean()) if ok.any() else float("nan")
+
+
+def saliency_from_attributions(initial, trained):
+    """The `initial_weights` / `trained_weights` / `change` block from two per-model dicts of saliency_report:
+    the change of the temporal concentration per split, of the clean-noisy cosine, and the cosine between the initial
+    and the trained class profile per split and class; every value a Python float or a list of them."""
+    pub = lambda m: {k: ({kk: (vv.tolist() if isinstance(vv, np.ndarray) else vv) for kk, vv in v.items()
+                          if not kk.startswith("_")} if isinstance(v, dict) else v) for k, v in m.items()}
+    change = {}
+    for s in ("clean", "noisy"):
+        a, b = initial[s], trained[s]
+        change[s] = {"temporal_concentration_change": b["temporal_concentration"] - a["temporal_concentration"],
+                     "class_profile_cosine": [_row_cosine(a["class_profile"][c:c + 1], b["class_profile"][c:c + 1])
+                                              for c in range(4)]}
+    if initial["clean_noisy_cosine"] is not None and trained["clean_noisy_cosine"] is not None:
+        change["clean_noisy_cosine_change"] = trained["clean_noisy_cosine"] - initial["clean_noisy_cosine"]
+    return {"initial_weights": pub(initial), "trained_weights": pub(trained), "change": change}
+
+
+def saliency_report(initial_model, trained_model, clean_split, noisy_split, target="pred", baseline=None):
+    """Which channels and frames carry the decision, for the initial and the trained weights on a clean and a noisy
+    split.  Per model and split: 'class_profile' [4][768] (the mean chan_attr per target class) and 'class_count',
+    'temporal_concentration' (the smallest share of an utterance's frames that holds half of sum_t |frame_attr_t|,
+    averaged over the utterances), 'max_completeness_gap'; per model 'clean_noisy_cosine' (the mean cosine between
+    the clean and the noisy chan_attr rows) where the two splits have the same lengths utterance for utterance, None
+    otherwise.  Host work on small tensors behind four integrated_gradients.  Returns saliency_from_attributions'
+    block."""
+    per = []
+    for model in (initial_model, trained_model):
+        c = _saliency_of(model, clean_split, target, baseline)
+        n = _saliency_of(model, noisy_split, target, baseline)
+        same = c["_lens"].shape == n["_lens"].shape and bool((c["_lens"] == n["_lens"]).all())
+        per.append({"clean": c, "noisy": n, "clean_noisy_cosine": _row_cosine(c["_chan"], n["_chan"]) if same else None})
+    return saliency_from_attributions(per[0], per[1])
