@@ -1174,6 +1174,100 @@ int dad_scl(const float* emb, const int64_t* labels, const uint8_t* member, int6
 int dad_scl_chunked(const float* emb, const int64_t* labels, const uint8_t* member, int64_t n, float tau, float* out,
                     float* grad, int chunks, void* workspace, void* stream);
 
+/* --- rank a split by a key and count positives along the order (csrc/rank.hip) -------------
+ * DACP keeps a pseudo-label when the teacher's certainty score clears a per-class quantile threshold
+ * (I/utils.py:449-507).  Whether that score is any good -- the coverage and purity a threshold buys, the split-wide
+ * quantiles, the wrong labels that pass, ROC-AUC, average precision, the risk-coverage curve, the reference's
+ * confidence_stats (I/inference.py:361-369) -- is one computation: put rows in a total order by a key and count
+ * positives along it.  m columns of n rows each, all inputs on the device and never written:
+ *   key [m][n] float32; flags [m][n] uint8 (DAD_RK_MEMBER | DAD_RK_POSITIVE); thr [m] float32 (NaN: no threshold);
+ *   gammas [Q] float32; B bins over [bin_lo, bin_hi), shared by the columns.
+ * Row i takes part in column j when its member bit is set and key[j][i] is finite (M rows; a member with a
+ * non-finite key is counted in DAD_RK_NONFINITE and left out).  The order of a column is over its M rows by
+ * (key descending, row index ascending); keys compare as values, so -0.0 equals +0.0 (and is reported as +0.0).
+ * Outputs per column (order, cum_pos, tie_end may each be NULL):
+ *   order [m][n] int32     the rows in order at positions 0 .. M-1, -1 behind them
+ *   cum_pos [m][n] int32   positives among positions 0 .. k; 0 at positions >= M
+ *   tie_end [m][n] uint8   1 where position k ends a run of equal keys: a curve is defined at these points only,
+ *                          which makes it independent of the order of the rows
+ *   counts [m][DAD_RK_COUNTS] int64, values [m][DAD_RK_VALUES] double: the slots below; an undefined value is 0
+ *   quant [m][Q] float32   torch.quantile(keys, gamma) (linear) of the M keys, in the float32 arithmetic of the
+ *                          step's DACP threshold: rank gamma (M - 1), lerp with the w < 0.5 branch; NaN for M = 0
+ *   bin_counts [m][B][2] int64 (rows, positives) and bin_sum [m][B] double (sum of the keys); the bin of a key is
+ *                          floor((double(key) - lo) / (hi - lo) * B) clamped to [0, B - 1]
+ * Every integer is exact.  Every double is a sum over the positions of the order in one fixed order that depends on
+ * nothing but the sorted sequence (no floating-point atomics): two calls, every chunk count and every permutation of
+ * the rows write the same bits to counts, values, quant and the bin blocks.  Enqueue-only on `stream`. */
+#define DAD_RK_MEMBERS 0          /* M: rows that take part */
+#define DAD_RK_POSITIVES 1        /* P: positives among them */
+#define DAD_RK_NONFINITE 2        /* members with a non-finite key (left out) */
+#define DAD_RK_RUNS 3             /* runs of equal keys */
+#define DAD_RK_U2 4               /* 2 #{key_p > key_q} + #{key_p = key_q} over (positive p, negative q): the
+                                     Mann-Whitney count, roc_auc_score = U2 / (2 P (M - P)) exactly */
+#define DAD_RK_ACCEPTED 5         /* rows with key >= thr (I/utils.py:501); 0 for a NaN thr */
+#define DAD_RK_ACCEPTED_POS 6     /* positives among them */
+#define DAD_RK_VALID_AUROC 7      /* 0 when P = 0 or P = M */
+#define DAD_RK_COUNTS 8
+#define DAD_RK_AUROC 0
+#define DAD_RK_AP 1               /* scikit-learn's average_precision_score: sum over runs of (R_r - R_{r-1}) P_r */
+#define DAD_RK_AURC 2             /* (1 / M) sum over runs of size_r (accepted_r - cum_pos_r) / accepted_r */
+#define DAD_RK_KEY_MEAN 3         /* the reference's confidence_stats: mean, population std, min, max */
+#define DAD_RK_KEY_STD 4
+#define DAD_RK_KEY_MIN 5
+#define DAD_RK_KEY_MAX 6
+#define DAD_RK_VALUES 8
+#define DAD_RK_MEMBER 1           /* flag bits */
+#define DAD_RK_POSITIVE 2
+#define DAD_RK_MAX_N 65536        /* largest n, as DAD_CM_MAX_N */
+#define DAD_RK_MAX_M 16           /* most columns */
+#define DAD_RK_MAX_Q 8            /* most quantiles */
+#define DAD_RK_MAX_BINS 64        /* most bins */
+#define DAD_RK_TILE 256           /* rows of a row tile / keys of a key tile of the counting pass */
+#define DAD_RK_MAX_CHUNKS 8       /* most chunks the key tiles of a row tile are split into */
+#define DAD_RK_EVAL_COLUMNS 10    /* columns dad_rank_eval_columns writes */
+typedef struct dad_rank_args {
+  const float* key;
+  const uint8_t* flags;
+  const float* thr;
+  const float* gammas;            /* may be NULL when Q = 0 */
+  int32_t* order;                 /* may be NULL */
+  int32_t* cum_pos;               /* may be NULL */
+  uint8_t* tie_end;               /* may be NULL */
+  int64_t* counts;
+  double* values;
+  float* quant;                   /* may be NULL when Q = 0 */
+  int64_t* bin_counts;            /* may be NULL when B = 0 */
+  double* bin_sum;                /* may be NULL when B = 0 */
+  int64_t n;
+  int32_t m, Q, B;
+  float bin_lo, bin_hi;
+  int32_t reserved;
+} dad_rank_args;
+/* workspace bytes of dad_rank_metrics (0 for an unsupported n or m); no initialisation needed */
+size_t dad_rank_workspace_bytes(int64_t n, int m);
+/* The grid of the counting pass for n rows and m columns on a device of `cus` compute units: workgroup
+ * (row tile, chunk, column), the key tiles of a column in `chunks` contiguous runs of `tiles_per_chunk` (no chunk
+ * empty), chunks <= min(row tiles, DAD_RK_MAX_CHUNKS).  Host only. */
+int dad_rank_plan(int64_t n, int m, int cus, int* row_tiles, int* chunks, int* tiles_per_chunk);
+/* DAD_E_ARG: args, workspace or a required pointer is NULL, or with B > 0 a range that is not finite with
+ * bin_lo < bin_hi; DAD_E_SHAPE: n outside [1, DAD_RK_MAX_N], m outside [1, DAD_RK_MAX_M], Q outside
+ * [0, DAD_RK_MAX_Q] or B outside [0, DAD_RK_MAX_BINS].  Nothing is launched on an error. */
+int dad_rank_metrics(const dad_rank_args* args, void* workspace, void* stream);
+/* dad_rank_metrics with the chunk count asked for (clamped as dad_rank_plan clamps it; <= 0: the plan's), for
+ * tests of the chunked counts at small n. */
+int dad_rank_metrics_chunked(const dad_rank_args* args, int chunks, void* workspace, void* stream);
+/* The ten standard columns of an evaluated split, key [10][n] and flags [10][n], from dad_eval_split's score [n],
+ * probs [n][4], pred [n] and labels [n] (one small kernel):
+ *   0     key = score, positive = the prediction is correct (selective classification)
+ *   1-4   key = score, member = pred is c, positive = label is c: DACP's per-class gate, precision is purity
+ *   5     key = max probability, positive = correct
+ *   6-9   key = p_c, positive = label is c (one-vs-rest)
+ * A row whose label or prediction is outside [0, 4) is a member of nothing.  labels NULL: every row (with a
+ * prediction in range) is a member and none is positive, so quantiles and gate counts still work on an unlabelled
+ * split.  DAD_E_ARG: score, probs, pred, key or flags is NULL; DAD_E_SHAPE: n outside [1, DAD_RK_MAX_N]. */
+int dad_rank_eval_columns(const float* score, const float* probs, const int64_t* pred, const int64_t* labels,
+                          int64_t n, float* key, uint8_t* flags, void* stream);
+
 /* --- the reference's helper types as operators (I/utils.py:317-652) -------------------
  * For trainer code that drives DataAugmentation / DACPManager / ECDALoss itself (the
  * train_step shim's callers, anchor calibration, I/train.py:334,341).  Same device functions

@@ -31,6 +31,8 @@ from .evaluate import (adversarial_response_curve, enqueue_input_grad, evaluate_
                        worst_case_report)
 from .evaluate import (attribution_plan, enqueue_attribution, integrated_gradients, saliency_from_attributions,
                        saliency_report)
+from .evaluate import (certainty_ranking_store, enqueue_certainty_ranking, firewall_report, rank_metrics,
+                       reliability_report, risk_coverage, roc_points)
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
            "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "SupervisedContrastiveLoss", "TrainingTrace",
@@ -45,6 +47,8 @@ __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "D
            "worst_case_report",
            "enqueue_attribution", "attribution_plan", "integrated_gradients", "saliency_report",
            "saliency_from_attributions",
+           "rank_metrics", "risk_coverage", "roc_points", "enqueue_certainty_ranking", "certainty_ranking_store",
+           "firewall_report", "reliability_report",
            "build", "lib"]
 
 

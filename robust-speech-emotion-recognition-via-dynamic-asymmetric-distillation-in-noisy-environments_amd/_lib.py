@@ -93,6 +93,14 @@ IG_FRAMES, IG_NONFINITE, IG_ZERO, IG_COUNTS = 0, 1, 2, 4
 AT_FRAMES, AT_NONFINITE, AT_CROSS, AT_ONE, AT_COUNTS = 0, 1, 2, 3, 4
 AT_PLAN_MODE, AT_PLAN_BYTES, AT_PLAN_LAUNCHES, AT_PLAN_KERNEL, AT_PLAN_SLOTS = 0, 1, 2, 3, 4
 
+# dad_rank_metrics (dad.h DAD_RK_*): the int64 slots of a column's counts, the float64 slots of its values, the flag
+# bits, the limits
+(RK_MEMBERS, RK_POSITIVES, RK_NONFINITE, RK_RUNS, RK_U2, RK_ACCEPTED, RK_ACCEPTED_POS, RK_VALID_AUROC,
+ RK_COUNTS) = range(9)
+RK_AUROC, RK_AP, RK_AURC, RK_KEY_MEAN, RK_KEY_STD, RK_KEY_MIN, RK_KEY_MAX, RK_VALUES = 0, 1, 2, 3, 4, 5, 6, 8
+RK_MEMBER, RK_POSITIVE = 1, 2
+RK_MAX_N, RK_MAX_M, RK_MAX_Q, RK_MAX_BINS, RK_TILE, RK_MAX_CHUNKS, RK_EVAL_COLUMNS = 65536, 16, 8, 64, 256, 8, 10
+
 
 class DadConfig(ctypes.Structure):
     _fields_ = [
@@ -200,6 +208,14 @@ class DadAttributionArgs(ctypes.Structure):
                   "utt_total", "counts")]
                 + [("n", ctypes.c_int64), ("slabs", ctypes.c_int64), ("store_dtype", ctypes.c_int32),
                    ("precision", ctypes.c_int32)])
+
+
+class DadRankArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_void_p) for n in
+                 ("key", "flags", "thr", "gammas", "order", "cum_pos", "tie_end", "counts", "values", "quant",
+                  "bin_counts", "bin_sum")]
+                + [("n", ctypes.c_int64), ("m", ctypes.c_int32), ("Q", ctypes.c_int32), ("B", ctypes.c_int32),
+                   ("bin_lo", ctypes.c_float), ("bin_hi", ctypes.c_float), ("reserved", ctypes.c_int32)])
 
 
 class DadTsneArgs(ctypes.Structure):
@@ -359,6 +375,14 @@ EXPORTS = {
     "dad_scl_chunked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_rank_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "dad_rank_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "dad_rank_metrics": (ctypes.c_int, [ctypes.POINTER(DadRankArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_rank_metrics_chunked": (ctypes.c_int, [ctypes.POINTER(DadRankArgs), ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
+    "dad_rank_eval_columns": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "dad_timing_start": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "dad_timing_kernels": (ctypes.c_int, [ctypes.c_uint]),
     "dad_timing_reset": (ctypes.c_int, []),
@@ -385,7 +409,9 @@ OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_step_plan_kernels", "dad_trace_
                     "dad_eval_windows_workspace_bytes", "dad_eval_windows",
                     "dad_eval_noise_workspace_bytes", "dad_eval_noise", "dad_eval_noise_draws",
                     "dad_input_grad_workspace_bytes", "dad_input_grad",
-                    "dad_attribution_workspace_bytes", "dad_attribution", "dad_attribution_plan")
+                    "dad_attribution_workspace_bytes", "dad_attribution", "dad_attribution_plan",
+                    "dad_rank_workspace_bytes", "dad_rank_plan", "dad_rank_metrics", "dad_rank_metrics_chunked",
+                    "dad_rank_eval_columns")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

@@ -62,6 +62,14 @@ csrc/attribution.hip):
   enqueue_attribution, attribution_plan, integrated_gradients, saliency_report, saliency_from_attributions
                       not in the reference: integrated gradients (Sundararajan et al. 2017) of a fixed logit
                       cotangent along the straight path from a baseline frame, in closed form
+
+and whether the certainty score that gates the pseudo-labels is any good, a split ranked by it (dad_rank_metrics,
+dad_rank_eval_columns, csrc/rank.hip):
+
+  rank_metrics, risk_coverage, roc_points, enqueue_certainty_ranking, certainty_ranking_store, firewall_report,
+  reliability_report  DACPManager.calculate_mask's gate on a whole split (I/utils.py:449-507), confidence_stats
+                      (I/inference.py:361-369); scikit-learn's roc_auc_score and average_precision_score, which the
+                      reference does not call
 """
 import ctypes
 import warnings
@@ -389,27 +397,42 @@ def metrics_from_confusion(cm):
 
 
 def validate_store(model, store_or_loader, domain_name="unknown", num_classes=4, teacher_disagreement=False,
-                   precision="fp32", cluster_metrics=False):
+                   precision="fp32", cluster_metrics=False, ranking=False):
     """validate() over a FeatureStore split in one fused pass: the same dict, 'disagreement_rate'
     from the same pass (the teacher runs on the student's row reads).  With cluster_metrics the dict
     gains 'silhouette_score' and 'calinski_harabasz_score' of the same pass's student embeddings
     (dad_cluster_metrics behind dad_eval_split on the stream; (0.0, 0.0) and a warning for a label
-    configuration the scores are not defined for)."""
+    configuration the scores are not defined for).  With ranking it gains 'auroc_ovr_macro' (scikit-learn's
+    roc_auc_score(y, probs, multi_class='ovr')), 'aurc' (the area under the risk-coverage curve of the certainty score)
+    and 'confidence_stats' (I/inference.py:361-369) of the same pass (dad_rank_eval_columns and dad_rank_metrics behind
+    dad_eval_split); without it nothing of that is launched or allocated."""
     if num_classes != 4:
         raise ValueError("the MI355X kernels are built for 4 classes")
     model.eval()
-    if not cluster_metrics:
+    if not cluster_metrics and not ranking:
         r = evaluate_store(model, store_or_loader, use_teacher=teacher_disagreement, precision=precision)
     else:
         plan = EvalPlan.of(store_or_loader)
         if plan.labels_d is None:
             raise ValueError("the split has no labels")
-        out = enqueue_eval_split(model, plan, teacher_disagreement, True, precision, ("emb",))
-        ws, block_d, block_h = plan.cluster_buffers()
-        _enqueue_cluster(out["emb"], plan.labels_d, block_d, None, ws)
-        block_h.copy_(block_d, non_blocking=True)
-        r = _read_eval_block(plan, {})          # (synchronises the stream: both blocks are on the host)
-        cm = _cluster_result(block_h.numpy().copy())
+        names = (("emb",) if cluster_metrics else ()) + (("score", "probs", "pred") if ranking else ())
+        out = enqueue_eval_split(model, plan, teacher_disagreement, True, precision, names)
+        if cluster_metrics:
+            ws, block_d, block_h = plan.cluster_buffers()
+            _enqueue_cluster(out["emb"], plan.labels_d, block_d, None, ws)
+            block_h.copy_(block_d, non_blocking=True)
+        if ranking:
+            rb = _ranking_buffers(plan, 0, 0)
+            rb["thr"].fill_(float("nan"))
+            _lib.check(_lib.require("dad_rank_eval_columns", "validate_store(ranking=True)")(
+                _lib.ptr(out["score"]), _lib.ptr(out["probs"]), _lib.ptr(out["pred"]), _lib.ptr(plan.labels_d), plan.n,
+                _lib.ptr(rb["key"]), _lib.ptr(rb["flags"]), torch.cuda.current_stream(plan.device).cuda_stream),
+                "dad_rank_eval_columns")
+            _enqueue_rank(rb["key"], rb["flags"], rb)
+            rb["block_h"].copy_(rb["block_d"], non_blocking=True)
+        r = _read_eval_block(plan, {})          # (synchronises the stream: every block is on the host)
+        if cluster_metrics:
+            cm = _cluster_result(block_h.numpy().copy())
     res = {}
     if teacher_disagreement:
         res["disagreement_rate"] = r["disagree"] / r["n"]
@@ -417,6 +440,11 @@ def validate_store(model, store_or_loader, domain_name="unknown", num_classes=4,
     if cluster_metrics:
         res["silhouette_score"] = cm["silhouette_score"]
         res["calinski_harabasz_score"] = cm["calinski_harabasz_score"]
+    if ranking:
+        rk = _certainty_result(_rank_columns(_rank_blocks(rb, rb["block_h"].numpy().copy())), (), 0)
+        res["auroc_ovr_macro"] = rk["ovr"]["auroc_macro"]
+        res["aurc"] = rk["selective"]["overall"]["aurc"]
+        res["confidence_stats"] = rk["confidence_stats"]
     return res
 
 
@@ -2253,3 +2281,318 @@ def saliency_report(initial_model, trained_model, clean_split, noisy_split, targ
         same = c["_lens"].shape == n["_lens"].shape and bool((c["_lens"] == n["_lens"]).all())
         per.append({"clean": c, "noisy": n, "clean_noisy_cosine": _row_cosine(c["_chan"], n["_chan"]) if same else None})
     return saliency_from_attributions(per[0], per[1])
+
+
+# ------------------------------------------------------------------ rank a split by certainty
+# DACP keeps a pseudo-label when the teacher's certainty score clears a per-class quantile threshold
+# (I/utils.py:449-507).  dad_rank_metrics (csrc/rank.hip) puts the rows of a split in a total order by a key
+# (descending, ties by row index, -0.0 == +0.0) and counts positives along it: the risk-coverage curve, ROC-AUC,
+# average precision, what a threshold accepts, torch.quantile in the step's float32 arithmetic, reliability bins and
+# the reference's confidence_stats (I/inference.py:361-369), every integer exact and every double bit-identical from
+# call to call.
+
+_RK_COLUMNS = _lib.RK_EVAL_COLUMNS
+
+
+def _rank_buffers(n, m, Q, B, curves, device):
+    """The buffers of one dad_rank_metrics call: 'block_d', one int64 tensor that holds counts [m][8] | values [m][8]
+    (float64) | bin_counts [m][B][2] | bin_sum [m][B] (float64) | quant [m][Q] (float32) so that one copy returns all
+    of it, its pinned host copy, thr, gammas, the curve tensors (curves) and the workspace."""
+    need = int(_lib.require("dad_rank_workspace_bytes", "rank_metrics")(int(n), int(m)))
+    if need == 0:
+        raise ValueError("rank metrics take 1 <= n <= %d rows and 1 <= m <= %d columns, got n = %d, m = %d"
+                         % (_lib.RK_MAX_N, _lib.RK_MAX_M, n, m))
+    if not 0 <= Q <= _lib.RK_MAX_Q or not 0 <= B <= _lib.RK_MAX_BINS:
+        raise ValueError("rank metrics take up to %d quantiles and %d bins" % (_lib.RK_MAX_Q, _lib.RK_MAX_BINS))
+    off = np.cumsum([0, m * _lib.RK_COUNTS, m * _lib.RK_VALUES, m * B * 2, m * B, (m * Q + 1) // 2]).tolist()
+    b = {"n": n, "m": m, "Q": Q, "B": B, "off": off,
+         "block_d": torch.zeros(max(off[-1], 1), dtype=torch.int64, device=device),
+         "block_h": torch.zeros(max(off[-1], 1), dtype=torch.int64).pin_memory(),
+         "thr": torch.full((m,), float("nan"), dtype=torch.float32, device=device),
+         "gammas": torch.zeros(max(Q, 1), dtype=torch.float32, device=device),
+         "ws": torch.empty(need, dtype=torch.uint8, device=device)}
+    if curves:
+        b["order"] = torch.empty(m, n, dtype=torch.int32, device=device)
+        b["cum_pos"] = torch.empty(m, n, dtype=torch.int32, device=device)
+        b["tie_end"] = torch.empty(m, n, dtype=torch.uint8, device=device)
+    return b
+
+
+def _enqueue_rank(key, flags, b, bin_range=(0.0, 1.0), chunks=0):
+    """dad_rank_metrics on the current stream, enqueue only; chunks > 0: dad_rank_metrics_chunked."""
+    a = _lib.DadRankArgs()
+    base, off = b["block_d"].data_ptr(), b["off"]
+    a.key, a.flags, a.thr = key.data_ptr(), flags.data_ptr(), b["thr"].data_ptr()
+    a.gammas = b["gammas"].data_ptr() if b["Q"] else None
+    for name in ("order", "cum_pos", "tie_end"):
+        setattr(a, name, b[name].data_ptr() if name in b else None)
+    a.counts, a.values = base + 8 * off[0], base + 8 * off[1]
+    a.bin_counts, a.bin_sum = (base + 8 * off[2], base + 8 * off[3]) if b["B"] else (None, None)
+    a.quant = base + 8 * off[4] if b["Q"] else None
+    a.n, a.m, a.Q, a.B = b["n"], b["m"], b["Q"], b["B"]
+    a.bin_lo, a.bin_hi = float(bin_range[0]), float(bin_range[1])
+    stream = torch.cuda.current_stream(key.device).cuda_stream
+    if chunks:
+        rc = _lib.require("dad_rank_metrics_chunked", "rank_metrics")(a, int(chunks), _lib.ptr(b["ws"]), stream)
+    else:
+        rc = _lib.require("dad_rank_metrics", "rank_metrics")(a, _lib.ptr(b["ws"]), stream)
+    _lib.check(rc, "dad_rank_metrics")
+
+
+def _rank_blocks(b, host):
+    """{'counts' [m][8] int64, 'values' [m][8] float64, 'bin_counts' [m][B][2], 'bin_sum' [m][B], 'quant' [m][Q]
+    float32} from the host copy of a call's block."""
+    m, Q, B, off = b["m"], b["Q"], b["B"], b["off"]
+    return {"counts": host[off[0]:off[1]].reshape(m, _lib.RK_COUNTS).copy(),
+            "values": host[off[1]:off[2]].view(np.float64).reshape(m, _lib.RK_VALUES).copy(),
+            "bin_counts": host[off[2]:off[3]].reshape(m, B, 2).copy(),
+            "bin_sum": host[off[3]:off[4]].view(np.float64).reshape(m, B).copy(),
+            "quant": host[off[4]:off[5]].view(np.float32)[:m * Q].reshape(m, Q).copy()}
+
+
+def _rank_columns(blocks, b=None):
+    """One dict per column from _rank_blocks; with the buffers b of a curves call the column's device rows too."""
+    cols = []
+    for j in range(len(blocks["counts"])):
+        c, v = blocks["counts"][j], blocks["values"][j]
+        col = {"members": int(c[_lib.RK_MEMBERS]), "positives": int(c[_lib.RK_POSITIVES]),
+               "nonfinite": int(c[_lib.RK_NONFINITE]), "runs": int(c[_lib.RK_RUNS]), "u2": int(c[_lib.RK_U2]),
+               "accepted": int(c[_lib.RK_ACCEPTED]), "accepted_positives": int(c[_lib.RK_ACCEPTED_POS]),
+               "auroc_valid": bool(c[_lib.RK_VALID_AUROC]), "auroc": float(v[_lib.RK_AUROC]),
+               "average_precision": float(v[_lib.RK_AP]), "aurc": float(v[_lib.RK_AURC]),
+               "key_mean": float(v[_lib.RK_KEY_MEAN]), "key_std": float(v[_lib.RK_KEY_STD]),
+               "key_min": float(v[_lib.RK_KEY_MIN]), "key_max": float(v[_lib.RK_KEY_MAX]),
+               "quantiles": blocks["quant"][j].copy(), "bin_counts": blocks["bin_counts"][j, :, 0].copy(),
+               "bin_positives": blocks["bin_counts"][j, :, 1].copy(), "bin_key_sum": blocks["bin_sum"][j].copy()}
+        if b is not None and "order" in b:
+            col.update(order=b["order"][j], cum_pos=b["cum_pos"][j], tie_end=b["tie_end"][j])
+        cols.append(col)
+    return cols
+
+
+def _read_rank(b, device):
+    b["block_h"].copy_(b["block_d"], non_blocking=True)
+    torch.cuda.current_stream(device).synchronize()
+    return _rank_blocks(b, b["block_h"].numpy().copy())
+
+
+def rank_metrics(keys, member, positive, thresholds=None, quantiles=(), bins=0, bin_range=(0.0, 1.0), curves=False,
+                 _chunks=0):
+    """dad_rank_metrics for columns of your own: keys [m, n] (or [n]) float32 on the device, member / positive boolean
+    [m, n] (or [n], shared by the columns), thresholds [m] (None: no threshold), quantiles up to 8 gammas, bins up to
+    64 over bin_range.  A row takes part in a column when it is a member with a finite key; the order is (key
+    descending, row index ascending).  Returns one dict per column: 'members', 'positives', 'nonfinite', 'runs', 'u2'
+    (the Mann-Whitney count), 'accepted' / 'accepted_positives' (key >= threshold), 'auroc_valid', 'auroc',
+    'average_precision', 'aurc', 'key_mean' / 'key_std' / 'key_min' / 'key_max', 'quantiles' [Q] (torch.quantile in
+    float32), 'bin_counts' / 'bin_positives' / 'bin_key_sum' [bins].  curves=True adds the device tensors 'order',
+    'cum_pos' and 'tie_end' [n] of the column, which risk_coverage(col) and roc_points(col) read at the tie ends."""
+    if not torch.is_tensor(keys) or not keys.is_cuda or keys.dtype != torch.float32 or keys.dim() not in (1, 2):
+        raise ValueError("keys must be a float32 device tensor [m, n] or [n]")
+    keys = keys.reshape(-1, keys.shape[-1]).contiguous()
+    m, n = keys.shape
+    dev = keys.device
+    flag = lambda t: torch.as_tensor(t).to(device=dev).to(torch.bool).expand(m, n)
+    flags = (flag(member).to(torch.uint8) * _lib.RK_MEMBER
+             + flag(positive).to(torch.uint8) * _lib.RK_POSITIVE).contiguous()
+    quantiles = [float(q) for q in quantiles]
+    b = _rank_buffers(n, m, len(quantiles), int(bins), curves, dev)
+    if thresholds is not None:
+        thr = torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1)
+        if thr.shape != (m,):
+            raise ValueError("thresholds must be [m]")
+        b["thr"].copy_(thr)
+    if quantiles:
+        b["gammas"].copy_(torch.tensor(quantiles, dtype=torch.float32))
+    _enqueue_rank(keys, flags, b, bin_range, _chunks)
+    return _rank_columns(_read_rank(b, dev), b)
+
+
+def risk_coverage(col):
+    """(coverage, risk) of a rank_metrics(curves=True) column at its tie ends, as float64 NumPy arrays: accepting the
+    k most certain rows covers k / M of the members with (k - positives among them) / k wrong."""
+    M = col["members"]
+    tie = col["tie_end"][:M].cpu().numpy().astype(bool)
+    taken = (np.nonzero(tie)[0] + 1).astype(np.float64)
+    return taken / max(M, 1), (taken - col["cum_pos"][:M].cpu().numpy()[tie]) / taken
+
+
+def roc_points(col):
+    """(false-positive rate, true-positive rate) of a rank_metrics(curves=True) column at its tie ends."""
+    M, P = col["members"], col["positives"]
+    tie = col["tie_end"][:M].cpu().numpy().astype(bool)
+    tp = col["cum_pos"][:M].cpu().numpy()[tie].astype(np.float64)
+    return (np.nonzero(tie)[0] + 1 - tp) / max(M - P, 1), tp / max(P, 1)
+
+
+def _ranking_buffers(plan, Q, B):
+    cache = plan.__dict__.setdefault("_rank", {})
+    b = cache.get((Q, B))
+    if b is None:
+        b = _rank_buffers(plan.n, _RK_COLUMNS, Q, B, False, plan.device)
+        b["key"] = torch.empty(_RK_COLUMNS, plan.n, dtype=torch.float32, device=plan.device)
+        b["flags"] = torch.empty(_RK_COLUMNS, plan.n, dtype=torch.uint8, device=plan.device)
+        cache[(Q, B)] = b
+    return b
+
+
+def _ranking_quantiles(quantiles, cfg):
+    if quantiles is None:
+        from .config import ConfigView
+        view = ConfigView(flavor="iemocap") if cfg is None else cfg
+        return [float(view.DACP_QUANTILE_START), float(view.DACP_QUANTILE_END)]
+    return [float(q) for q in quantiles]
+
+
+def enqueue_certainty_ranking(model, plan, use_teacher=False, thresholds=None, quantiles=None, bins=20,
+                              precision="fp32", cfg=None, outputs=()):
+    """The enqueue part of certainty_ranking_store (no copy to the host, no synchronisation): one dad_eval_split, with
+    use_teacher dad_predict_head on its t_emb for the teacher's probabilities and score, then dad_rank_eval_columns and
+    dad_rank_metrics behind it on the current stream.  Returns (buffers, {name: device tensor}) with 'score', 'probs',
+    'pred' (the ranked model's) and the further `outputs` of dad_eval_split; the block lands in buffers['block_d']."""
+    gam = _ranking_quantiles(quantiles, cfg)
+    b = _ranking_buffers(plan, len(gam), int(bins))
+    names = set(outputs) | ({"t_emb"} if use_teacher else {"score", "probs", "pred"})
+    out = enqueue_eval_split(model, plan, use_teacher=use_teacher, precision=precision, outputs=tuple(sorted(names)))
+    stream = torch.cuda.current_stream(plan.device).cuda_stream
+    if use_teacher:
+        cls = model.teacher_classifier
+        w2, b2 = cls.fc_layer.weight.detach().contiguous(), cls.fc_layer.bias.detach().contiguous()
+        head = {"probs": torch.empty(plan.n, 4, device=plan.device), "score": torch.empty(plan.n, device=plan.device),
+                "pred": torch.empty(plan.n, dtype=torch.int64, device=plan.device)}
+        _lib.check(_lib.lib().dad_predict_head(_lib.ptr(out["t_emb"]), plan.n, _lib.ptr(w2), _lib.ptr(b2), 1, None,
+                                               _lib.ptr(head["probs"]), _lib.ptr(head["score"]),
+                                               _lib.ptr(head["pred"]), stream), "dad_predict_head")
+        out.update(head)
+    b["thr"].fill_(float("nan"))
+    if thresholds is not None:
+        thr = torch.as_tensor(thresholds).detach().to(device=plan.device, dtype=torch.float32).reshape(-1)
+        if thr.shape != (4,):
+            raise ValueError("thresholds must be [4]")
+        b["thr"][1:5].copy_(thr)
+    if gam:
+        b["gammas"].copy_(torch.tensor(gam, dtype=torch.float32), non_blocking=False)
+    _lib.check(_lib.require("dad_rank_eval_columns", "certainty ranking")(
+        _lib.ptr(out["score"]), _lib.ptr(out["probs"]), _lib.ptr(out["pred"]), _lib.ptr(plan.labels_d), plan.n,
+        _lib.ptr(b["key"]), _lib.ptr(b["flags"]), stream), "dad_rank_eval_columns")
+    _enqueue_rank(b["key"], b["flags"], b)
+    return b, out
+
+
+def _ratio(a, d):
+    return float(a) / float(d) if d else 0.0
+
+
+def _certainty_result(cols, gam, bins):
+    """certainty_ranking_store's dict from the ten columns of dad_rank_eval_columns."""
+    sel = lambda c: {"aurc": c["aurc"], "auroc": c["auroc"], "auroc_valid": c["auroc_valid"],
+                     "accuracy": _ratio(c["positives"], c["members"]), "n": c["members"]}
+    gate = []
+    for c in cols[1:5]:
+        M, P, A, AP = c["members"], c["positives"], c["accepted"], c["accepted_positives"]
+        wrong = M - P
+        gate.append({"members": M, "passed": A, "passed_right": AP, "passed_wrong": A - AP, "blocked_right": P - AP,
+                     "blocked_wrong": wrong - (A - AP), "purity": _ratio(AP, A), "coverage": _ratio(A, M),
+                     "leak": _ratio(A - AP, wrong)})
+    ovr = cols[6:10]
+    conf = cols[5]
+    edges = np.linspace(0.0, 1.0, bins + 1) if bins else np.zeros(0)
+    rel = {"edges": edges.tolist(), "count": conf["bin_counts"].tolist(),
+           "accuracy": [_ratio(p, k) for p, k in zip(conf["bin_positives"], conf["bin_counts"])],
+           "confidence": [_ratio(s, k) for s, k in zip(conf["bin_key_sum"], conf["bin_counts"])]}
+    n = max(conf["members"], 1)
+    rel["ece"] = float(sum(k / n * abs(a - c) for k, a, c in zip(rel["count"], rel["accuracy"], rel["confidence"])))
+    return {
+        "selective": {"overall": sel(cols[0]), "per_class": [sel(c) for c in cols[1:5]],
+                      "max_probability": sel(cols[5])},
+        "ovr": {"auroc_per_class": [c["auroc"] for c in ovr], "ap_per_class": [c["average_precision"] for c in ovr],
+                "auroc_macro": float(np.mean([c["auroc"] for c in ovr])),
+                "ap_macro": float(np.mean([c["average_precision"] for c in ovr])),
+                "valid": all(c["auroc_valid"] for c in ovr)},
+        "confidence_stats": {"mean_confidence": conf["key_mean"], "std_confidence": conf["key_std"],
+                             "min_confidence": conf["key_min"], "max_confidence": conf["key_max"]},
+        "gate": gate,
+        "quantiles": list(gam),
+        "quantile_thresholds": np.stack([c["quantiles"] for c in cols[1:5]]),
+        "reliability": rel,
+        "columns": cols,
+    }
+
+
+def certainty_ranking_store(model, store_or_loader, use_teacher=False, thresholds=None, quantiles=None, bins=20,
+                            precision="fp32", cfg=None, outputs=()):
+    """How good the score that gates training is, over a whole split: one dad_eval_split, dad_rank_eval_columns and
+    dad_rank_metrics on the stream, one copy back.  With use_teacher the teacher is ranked (its probabilities and
+    score from dad_predict_head on t_emb).  quantiles None: DACP_QUANTILE_START and DACP_QUANTILE_END of the config.
+    thresholds [4] (DADStep.ema_thresholds, the calibrated anchors): applied per predicted class, score >= tau
+    (I/utils.py:501).  Returns
+      'selective'  overall / per predicted class / by max probability: AURC, the AUROC of the score as a detector of
+                   correct predictions, the accuracy at full coverage
+      'ovr'        per-class one-vs-rest AUROC and AP, their macro means (roc_auc_score(y, probs, multi_class='ovr'))
+      'confidence_stats'  the reference's four keys (I/inference.py:361-369), of the max probability
+      'gate'       per class: members, passed, passed_right, passed_wrong, blocked_right, blocked_wrong, purity,
+                   coverage, leak = wrong passed / wrong
+      'quantile_thresholds' [4][Q]  torch.quantile(class scores, gamma) of I/utils.py:477-481 on the whole split
+      'reliability'  the bins of the max probability: edges, count, accuracy, confidence, ece
+      'columns'    the ten raw columns, plus a device tensor per name in `outputs` and 'score', 'probs', 'pred'.
+    An unlabelled split gives the quantiles and the gate's passed counts; what needs labels is 0."""
+    model.eval()
+    plan = EvalPlan.of(store_or_loader)
+    b, out = enqueue_certainty_ranking(model, plan, use_teacher, thresholds, quantiles, bins, precision, cfg, outputs)
+    b["block_h"].copy_(b["block_d"], non_blocking=True)
+    _read_eval_block(plan, {})        # (synchronises the stream; raises on a non-finite logit)
+    cols = _rank_columns(_rank_blocks(b, b["block_h"].numpy().copy()))
+    res = _certainty_result(cols, _ranking_quantiles(quantiles, cfg), int(bins))
+    res.update(out)
+    return res
+
+
+def _firewall_of(model, split, thresholds):
+    r = certainty_ranking_store(model, split, use_teacher=True, thresholds=thresholds)
+    g = r["gate"]
+    tot = lambda k: sum(c[k] for c in g)
+    wrong = tot("passed_wrong") + tot("blocked_wrong")
+    return {"passed": float(tot("passed")), "passed_wrong": float(tot("passed_wrong")),
+            "coverage": _ratio(tot("passed"), tot("members")), "purity": _ratio(tot("passed_right"), tot("passed")),
+            "leak": _ratio(tot("passed_wrong"), wrong), "teacher_aurc": r["selective"]["overall"]["aurc"],
+            "teacher_auroc": r["selective"]["overall"]["auroc"],
+            "purity_per_class": [c["purity"] for c in g], "coverage_per_class": [c["coverage"] for c in g],
+            "leak_per_class": [c["leak"] for c in g], "gate": g}
+
+
+def _house_report(initial, trained, keys):
+    pick = lambda r: {k: r[k] for k in r if k != "gate"}
+    return {"initial_weights": pick(initial), "trained_weights": pick(trained),
+            "improvement": {k + "_change": float(trained[k] - initial[k]) for k in keys}}
+
+
+def firewall_report(model, noisy_split, thresholds, initial_model=None):
+    """The pseudo-label firewall split-wide: the teacher on the noisy split at the thresholds tau [4] -- how many
+    pseudo-labels pass the gate, how pure they are and which share of the wrong ones leaks through (the confirmation
+    bias analyze_confirmation_bias.py follows on 50 tracked samples).  `model` is the trained model; initial_model
+    (None: the same model, so every change is 0) gives the `initial_weights` block.  Every value a Python float or a
+    list of them; 'gate' (the per-class integer counts of the trained model) rides along at the top level."""
+    trained = _firewall_of(model, noisy_split, thresholds)
+    initial = trained if initial_model is None else _firewall_of(initial_model, noisy_split, thresholds)
+    rep = _house_report(initial, trained, ("coverage", "purity", "leak", "teacher_aurc", "teacher_auroc"))
+    rep["gate"] = trained["gate"]
+    return rep
+
+
+def _reliability_of(model, clean_split, noisy_split):
+    res = {}
+    for name, split in (("clean", clean_split), ("noisy", noisy_split)):
+        r = certainty_ranking_store(model, split)
+        res.update({name + "_aurc": r["selective"]["overall"]["aurc"],
+                    name + "_auroc": r["selective"]["overall"]["auroc"],
+                    name + "_ece": r["reliability"]["ece"], name + "_auroc_ovr_macro": r["ovr"]["auroc_macro"],
+                    name + "_mean_confidence": r["confidence_stats"]["mean_confidence"]})
+    return res
+
+
+def reliability_report(initial_model, trained_model, clean_split, noisy_split):
+    """Whether the student's certainty can be trusted, for the initial and the trained weights on a clean and a noisy
+    split: AURC, the AUROC of the score as a detector of correct predictions, the expected calibration error of the max
+    probability, the macro one-vs-rest AUROC and the mean confidence, in the house format."""
+    a = _reliability_of(initial_model, clean_split, noisy_split)
+    b = _reliability_of(trained_model, clean_split, noisy_split)
+    return _house_report(a, b, tuple(a))
