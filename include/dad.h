@@ -719,6 +719,93 @@ int dad_eval_noise(const dad_noise_args* args, void* workspace, void* stream);
  * NULL; DAD_E_SHAPE as above (levels taken as 1). */
 int dad_eval_noise_draws(const dad_noise_args* args, float* out, void* stream);
 
+/* --- several networks on one split: up to 8 checkpoints in one store pass (csrc/eval_models.hip) ----
+ * The reference compares networks on the same split everywhere around its train step: the fold checkpoints
+ * (best_model_fold_k.ckpt), the ablation runners' BEST checkpoints, inference.py's weights one after another, the
+ * student / teacher pair.  dad_eval_models evaluates K networks on a split in one call and leaves what such a
+ * comparison reads in one result block: who is better, whether the difference is more than chance (McNemar's two
+ * cells), how often two networks disagree, and what their ensemble and their majority vote would score.
+ *
+ * Members.  m < K is model k = m; m = K is the mean ensemble; m = K + 1 is the vote.
+ * Per model k: emb / logits / probs / score / pred [k][n] are dad_eval_split's for student = models[k], bit for bit,
+ * in both precisions and for the three store types (the same loaders, k order, epilogue order and head; the slab
+ * kernel runs two consecutive slab jobs per wave on one W1 fragment, which changes no accumulator's chain).  An
+ * utterance of length 0, or one whose slab_off entries disagree with its length, has a zero embedding and logits =
+ * b2 of every model.
+ * Mean ensemble: w^_k = (float)(weight[k] / sum_j weight[j]), the quotient in double on the host (sum in k order);
+ *   ens_probs[c] is the fp32 chain e = 0; e = fmaf(w^_k, p_k[c], e) for k = 0 .. K - 1; ens_pred its first-maximum
+ *   argmax; ens_score the head's certainty formula on ens_probs (max_c e_c * (1 - H_2(e + 1e-8) / 2), or max_c e_c
+ *   without use_entropy).  With K = 1, ens_probs equals probs[0] bit for bit.
+ * Vote: votes[u][c] is the number of models with pred_k = c; vote_pred is the class with most votes, ties to the
+ *   lowest class index (dad_knn_vote's and dad_eval_windows' rule).  n_correct[u] is the number of models that are
+ *   right, or -1 for an utterance without a label in [0, 4).
+ *
+ * counts[DAD_EM_COUNTS] int64: the layout does not depend on K; entries of unused members are written 0. */
+#define DAD_EM_MAX_MODELS 8
+#define DAD_EM_MEMBERS 10       /* K models, then the mean ensemble (index K), then the vote (index K + 1) */
+#define DAD_EM_CONF 0           /* [10][4][4] per member: row = label, column = prediction (labelled utterances) */
+#define DAD_EM_DISAGREE 160     /* [10][10] pred_a != pred_b, over all n utterances */
+#define DAD_EM_ONLY 260         /* [10][10] labelled utterances where a is right and b is wrong; the diagonal is a's
+                                   correct count; ONLY[a][b] and ONLY[b][a] are McNemar's two cells */
+#define DAD_EM_HIST 360         /* [9] labelled utterances by how many of the K models are right */
+#define DAD_EM_N 369            /* n */
+#define DAD_EM_N_LABELLED 370   /* utterances with a label in [0, 4) */
+#define DAD_EM_N_SKIPPED 371    /* label outside [0, 4), or labels == NULL (then n) */
+#define DAD_EM_NONFINITE 372    /* [8] per model: utterances with a logit that is not finite */
+#define DAD_EM_K 380            /* K */
+#define DAD_EM_COUNTS 384       /* int64 slots of the counts block (381..383 reserved, written 0) */
+/* sums[DAD_EM_SUMS] double, [quantity][member], members m <= K (the vote has no probabilities; its slots and those
+ * of unused members are written 0).  Every term is computed in double from the float32 probabilities (the score from
+ * the float32 score) and summed in a fixed order (strided per-thread sums and an LDS tree, as dad_eval_split's
+ * moments): no floating-point atomics, two calls give the same bits. */
+#define DAD_EM_SUM_SCORE 0      /* [10] certainty score, over all n */
+#define DAD_EM_SUM_ENTROPY 10   /* [10] -sum_c p_c ln p_c (0 ln 0 = 0), over all n */
+#define DAD_EM_SUM_NLL 20       /* [10] -ln p_y, over labelled utterances */
+#define DAD_EM_SUM_BRIER 30     /* [10] sum_c (p_c - [y = c])^2, over labelled utterances */
+#define DAD_EM_SUMS 40
+/* Rows as dad_eval_args (store, rows, lens, labels, slab_off, slabs).  Enqueue only, no allocation, no device read
+ * on the host.  Per-model outputs are model-major (dad_eval_noise's [K][n] layout); every output but counts and sums
+ * is optional (NULL = not written). */
+typedef struct dad_models_args {
+  const void* store;            /* [frames][768], dtype store_dtype */
+  const int64_t* rows;          /* [n] store row of frame 0 */
+  const int32_t* lens;          /* [n] frames */
+  const int64_t* labels;        /* [n] or NULL */
+  const int32_t* slab_off;      /* [n + 1] exclusive prefix of ceil(lens / 32) */
+  int64_t n;                    /* utterances, >= 1 */
+  int64_t slabs;                /* slab_off[n] */
+  int32_t store_dtype;          /* DAD_STORE_* */
+  int32_t use_entropy;          /* USE_ENTROPY_IN_SCORE */
+  int32_t precision;            /* DAD_PREC_FP32 or DAD_PREC_FP16 */
+  int32_t reserved0;
+  const float* models[DAD_EM_MAX_MODELS];   /* device, flat [W1|b1|W2|b2]; entries >= K ignored; may repeat */
+  float weight[DAD_EM_MAX_MODELS];  /* [K] host values, the ensemble weights: finite, >= 0, sum > 0 */
+  int32_t K;                    /* models, in [1, DAD_EM_MAX_MODELS] */
+  int32_t reserved1;
+  /* per-model outputs */
+  float* emb;                   /* [K][n][256] */
+  float* logits;                /* [K][n][4] */
+  float* probs;                 /* [K][n][4] */
+  float* score;                 /* [K][n] */
+  int64_t* pred;                /* [K][n] */
+  /* per-utterance outputs */
+  float* ens_probs;             /* [n][4] */
+  float* ens_score;             /* [n] */
+  int64_t* ens_pred;            /* [n] */
+  int64_t* vote_pred;           /* [n] */
+  int32_t* votes;               /* [n][4] */
+  int32_t* n_correct;           /* [n], -1 unlabelled */
+  int64_t* counts;              /* [DAD_EM_COUNTS], required */
+  double* sums;                 /* [DAD_EM_SUMS], required */
+} dad_models_args;
+/* workspace bytes of dad_eval_models: K * slabs * 1 KB of slab partials, per-utterance words and, in DAD_PREC_FP16,
+ * K fp16 copies of W1 (0 for unsupported sizes or K); no initialisation needed */
+size_t dad_eval_models_workspace_bytes(int64_t n, int64_t slabs, int K, int precision);
+/* Checked on the host before anything is launched.  DAD_E_ARG: a required pointer is NULL, K outside [1, 8], a
+ * models[k] (k < K) NULL, a weight negative or not finite, sum of the weights 0, an unknown dtype / precision;
+ * DAD_E_SHAPE: n < 1, slabs outside [0, n * 2^26], or K * slabs * 256 >= 2^31; DAD_E_UNSUPPORTED: DAD_PREC_BF16. */
+int dad_eval_models(const dad_models_args* args, void* workspace, void* stream);
+
 /* --- input gradients of a split: the worst-case direction, store-fed (csrc/input_grad.hip) ----
  * dad_eval_noise measures a split under RANDOM noise.  dad_input_grad gives the direction of the WORST perturbation
  * of the same size: the vector-Jacobian product of the eval-mode forward (SSRLModel.predict, I/model.py:225-245)

@@ -33,6 +33,7 @@ from .evaluate import (attribution_plan, enqueue_attribution, integrated_gradien
                        saliency_report)
 from .evaluate import (certainty_ranking_store, enqueue_certainty_ranking, firewall_report, rank_metrics,
                        reliability_report, risk_coverage, roc_points)
+from .evaluate import enqueue_eval_models, ensemble_report, evaluate_models_store
 
 __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "DPComm", "ProcessGroupComm", "ConfigView",
            "dad_config_for", "FLAVOR_DEFAULTS", "FeatureStore", "DeviceLoader", "DataAugmentation", "DACPManager", "ECDALoss", "SupervisedContrastiveLoss", "TrainingTrace",
@@ -49,6 +50,7 @@ __all__ = ["SSRLModel", "Emotion2VecEncoder", "EmotionClassifier", "DADStep", "D
            "saliency_from_attributions",
            "rank_metrics", "risk_coverage", "roc_points", "enqueue_certainty_ranking", "certainty_ranking_store",
            "firewall_report", "reliability_report",
+           "enqueue_eval_models", "evaluate_models_store", "ensemble_report",
            "build", "lib"]
 
 

@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_DIR = os.path.join(os.path.dirname(PKG_DIR), "lib")
 OBJ_DIR = os.path.join(PKG_DIR, "build")
 LIB_PATH = os.path.join(LIB_DIR, "libdad_hip.so")
-SOURCES = ["encode.hip", "encode_ws.hip", "tail_general.hip", "tail_w.hip", "tail_w_s16.hip", "wgrad_f32.hip", "wgrad_direct.hip", "reduce.hip", "optim.hip", "dad_abi.hip", "timing.hip", "encoder_ops.hip", "rccl_dp.hip", "collate.hip", "eval.hip", "utils_abi.hip", "prep.hip", "eval_split.hip", "trace.hip", "pairwise.hip", "cluster.hip", "tsne.hip", "domain_gap.hip", "knn.hip", "scl.hip", "eval_windows.hip", "eval_noise.hip", "input_grad.hip", "attribution.hip", "rank.hip",
+SOURCES = ["encode.hip", "encode_ws.hip", "tail_general.hip", "tail_w.hip", "tail_w_s16.hip", "wgrad_f32.hip", "wgrad_direct.hip", "reduce.hip", "optim.hip", "dad_abi.hip", "timing.hip", "encoder_ops.hip", "rccl_dp.hip", "collate.hip", "eval.hip", "utils_abi.hip", "prep.hip", "eval_split.hip", "trace.hip", "pairwise.hip", "cluster.hip", "tsne.hip", "domain_gap.hip", "knn.hip", "scl.hip", "eval_windows.hip", "eval_noise.hip", "input_grad.hip", "attribution.hip", "rank.hip", "eval_models.hip",
            "encode_ws_rg.hip", "wgrad_direct_rg.hip", "tail_w_rg.hip", "prep_rg.hip"]   # (the ragged step's `_rg` sibling kernels)
 HEADERS = ["dad_common.h", "dad_kernels.h", "dad_probe.h", "dad_prep.h", "step_plan.h", "dad_host.h", "dad_timing.h",
            "tail_common.h", "pool.h", "wgrad_common.h", "wgrad_direct.h", "pairwise.h", "scl.h", "eval_rows.h", "tail_w.hip", "encode_ws.hip",

@@ -85,6 +85,12 @@ EN_MAX_LEVELS = 8
 EN_CONF, EN_FLIPS, EN_SURVIVE = 0, 128, 136
 EN_N, EN_N_LABELLED, EN_N_SKIPPED, EN_N_NONFINITE, EN_LEVELS, EN_COUNTS = 144, 145, 146, 147, 148, 160
 EN_SUM_SCORE, EN_SUM_DRIFT, EN_SUM_KL, EN_SUMS = 0, 8, 16, 24
+# dad_eval_models (dad.h DAD_EM_*): the model limit, the members (K models, the mean ensemble at K, the vote at K + 1),
+# the int64 slots of the counts block and the float64 slots of the sums ([quantity][member])
+EM_MAX_MODELS, EM_MEMBERS = 8, 10
+EM_CONF, EM_DISAGREE, EM_ONLY, EM_HIST = 0, 160, 260, 360
+EM_N, EM_N_LABELLED, EM_N_SKIPPED, EM_NONFINITE, EM_K, EM_COUNTS = 369, 370, 371, 372, 380, 384
+EM_SUM_SCORE, EM_SUM_ENTROPY, EM_SUM_NLL, EM_SUM_BRIER, EM_SUMS = 0, 10, 20, 30, 40
 
 # dad_input_grad (dad.h DAD_IG_*): the int64 slots of the counts block
 IG_FRAMES, IG_NONFINITE, IG_ZERO, IG_COUNTS = 0, 1, 2, 4
@@ -194,6 +200,17 @@ class DadNoiseArgs(ctypes.Structure):
                 + [(n, ctypes.c_int32) for n in ("levels", "store_dtype", "use_entropy", "precision")])
 
 
+class DadModelsArgs(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("store", "rows", "lens", "labels", "slab_off")]
+                + [("n", ctypes.c_int64), ("slabs", ctypes.c_int64)]
+                + [(n, ctypes.c_int32) for n in ("store_dtype", "use_entropy", "precision", "reserved0")]
+                + [("models", ctypes.c_void_p * EM_MAX_MODELS), ("weight", ctypes.c_float * EM_MAX_MODELS),
+                   ("K", ctypes.c_int32), ("reserved1", ctypes.c_int32)]
+                + [(n, ctypes.c_void_p) for n in
+                   ("emb", "logits", "probs", "score", "pred", "ens_probs", "ens_score", "ens_pred", "vote_pred",
+                    "votes", "n_correct", "counts", "sums")])
+
+
 class DadInputGradArgs(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_void_p) for n in
                  ("store", "rows", "lens", "slab_off", "params", "dz", "delta_in", "grad", "delta_out", "frame_l1",
@@ -301,6 +318,8 @@ EXPORTS = {
     "dad_eval_noise_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     "dad_eval_noise": (ctypes.c_int, [ctypes.POINTER(DadNoiseArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "dad_eval_noise_draws": (ctypes.c_int, [ctypes.POINTER(DadNoiseArgs), ctypes.c_void_p, ctypes.c_void_p]),
+    "dad_eval_models_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "dad_eval_models": (ctypes.c_int, [ctypes.POINTER(DadModelsArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "dad_input_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "dad_input_grad": (ctypes.c_int, [ctypes.POINTER(DadInputGradArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "dad_attribution_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
@@ -411,7 +430,7 @@ OPTIONAL_EXPORTS = ("dad_step_ragged_plan", "dad_step_plan_kernels", "dad_trace_
                     "dad_input_grad_workspace_bytes", "dad_input_grad",
                     "dad_attribution_workspace_bytes", "dad_attribution", "dad_attribution_plan",
                     "dad_rank_workspace_bytes", "dad_rank_plan", "dad_rank_metrics", "dad_rank_metrics_chunked",
-                    "dad_rank_eval_columns")
+                    "dad_rank_eval_columns", "dad_eval_models_workspace_bytes", "dad_eval_models")
 
 # per-kernel timing slots (dad.h DAD_TK_*)
 TK_NAMES = ["encode", "pool", "tail", "wgrad", "reduce", "optim"]

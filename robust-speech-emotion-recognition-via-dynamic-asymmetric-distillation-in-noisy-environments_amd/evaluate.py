@@ -70,8 +70,15 @@ dad_rank_eval_columns, csrc/rank.hip):
   reliability_report  DACPManager.calculate_mask's gate on a whole split (I/utils.py:449-507), confidence_stats
                       (I/inference.py:361-369); scikit-learn's roc_auc_score and average_precision_score, which the
                       reference does not call
+
+and several networks on one split, up to 8 checkpoints in one store pass (dad_eval_models, csrc/eval_models.hip):
+
+  enqueue_eval_models, evaluate_models_store, ensemble_report
+                      what the reference does one network at a time: the fold checkpoints (best_model_fold_k.ckpt),
+                      the ablation runners' BEST checkpoints, inference.py's weights over the same test sets
 """
 import ctypes
+import math
 import warnings
 
 import numpy as np
@@ -2596,3 +2603,229 @@ def reliability_report(initial_model, trained_model, clean_split, noisy_split):
     a = _reliability_of(initial_model, clean_split, noisy_split)
     b = _reliability_of(trained_model, clean_split, noisy_split)
     return _house_report(a, b, tuple(a))
+
+
+# ------------------------------------------------------------------ several networks on one split
+# The reference compares networks on the same split everywhere around its train step (fold checkpoints, ablation
+# runners, inference.py, student / teacher).  dad_eval_models (csrc/eval_models.hip) evaluates up to 8 of them in
+# one pass over the store and builds what a comparison reads on the device: per-member confusion matrices (the K
+# models, their mean ensemble, their vote), pairwise disagreement and McNemar cells, the correct-count histogram
+# and the float64 sums behind mean NLL, Brier score and entropy.  Definitions: include/dad.h, "several networks on
+# one split".
+
+_MODELS_OUTPUTS = {"emb": ((256,), torch.float32), "logits": ((4,), torch.float32), "probs": ((4,), torch.float32),
+                   "score": ((), torch.float32), "pred": ((), torch.int64)}
+_MODELS_UTT_OUTPUTS = {"ens_probs": ((4,), torch.float32), "ens_score": ((), torch.float32),
+                       "ens_pred": ((), torch.int64), "vote_pred": ((), torch.int64), "votes": ((4,), torch.int32),
+                       "n_correct": ((), torch.int32)}
+_MODELS_WORDS = _lib.EM_COUNTS + _lib.EM_SUMS
+
+
+def _models_buffers(plan):
+    """The buffers of dad_eval_models over this split, kept on the plan beside the noise buffers: {'result_d' /
+    'result_h' the DAD_EM_* block (counts, then sums) and its pinned host copy, 'ws' the workspace, 'scratch' the
+    model that checkpoint paths are loaded into, 'flats' the device copies of their weights}."""
+    b = plan._noise.get("models")
+    if b is None:
+        b = {"result_d": torch.zeros(_MODELS_WORDS, dtype=torch.int64, device=plan.device),
+             "result_h": torch.zeros(_MODELS_WORDS, dtype=torch.int64).pin_memory(), "ws": None, "scratch": None,
+             "flats": {}}
+        plan._noise["models"] = b
+    return b
+
+
+def _model_flats(models, plan):
+    """The flat [W1|b1|W2|b2] device tensor of every entry of `models`: an SSRLModel (its student), a (model,
+    'student' | 'teacher') pair, a flat float32 device tensor, or a checkpoint path (loaded with
+    checkpoint.load_checkpoint into a scratch model; its student weights are copied to a tensor kept on the plan)."""
+    from .model import SSRLModel
+    models = list(models)
+    if not 1 <= len(models) <= _lib.EM_MAX_MODELS:
+        raise ValueError("between 1 and %d models, got %d" % (_lib.EM_MAX_MODELS, len(models)))
+    nparam = int(_lib.lib().dad_param_count())
+    flats = []
+    for i, m in enumerate(models):
+        if isinstance(m, tuple):
+            mod, role = m
+            if role not in ("student", "teacher"):
+                raise ValueError("models[%d]: the role is 'student' or 'teacher', got %r" % (i, role))
+            f = mod.teacher_flat if role == "teacher" else mod.student_flat
+        elif isinstance(m, torch.Tensor):
+            f = m
+        elif isinstance(m, (str, bytes)) or hasattr(m, "__fspath__"):
+            from . import checkpoint
+            b = _models_buffers(plan)
+            if b["scratch"] is None:
+                b["scratch"] = SSRLModel().to(plan.device)
+            checkpoint.load_checkpoint(m, b["scratch"])
+            f = b["flats"].setdefault(i, torch.empty(nparam, dtype=torch.float32, device=plan.device))
+            f.copy_(b["scratch"].student_flat.detach())
+        elif hasattr(m, "student_flat"):
+            f = m.student_flat
+        else:
+            raise TypeError("models[%d]: an SSRLModel, a (model, role) pair, a flat tensor or a checkpoint path, got %s"
+                            % (i, type(m).__name__))
+        f = f.detach()
+        if (f.dtype != torch.float32 or f.device != plan.device or not f.is_contiguous() or f.numel() != nparam):
+            raise ValueError("models[%d]: a contiguous float32 tensor of %d parameters on %s is needed"
+                             % (i, nparam, plan.device))
+        flats.append(f)
+    return flats
+
+
+def _models_weights(weights, K):
+    w = [1.0] * K if weights is None else [float(v) for v in np.asarray(weights, dtype=np.float64).reshape(-1)]
+    if len(w) != K:
+        raise ValueError("%d weights for %d models" % (len(w), K))
+    if any(not np.isfinite(v) or v < 0 for v in w) or not sum(w) > 0:
+        raise ValueError("ensemble weights must be finite, >= 0 and not all zero, got %r" % (w,))
+    return w
+
+
+def enqueue_eval_models(models, plan, weights=None, use_entropy=True, precision="fp32", outputs=(), _block=None):
+    """dad_eval_models on the current stream, enqueue only (no copy, no synchronisation): `models` (1 to 8 entries,
+    _model_flats' forms; the same network may appear twice) over the plan's split, `weights` the ensemble weights
+    (None: equal).  The DAD_EM_* block lands in the plan's buffer (or in _block, an int64 device tensor of EM_COUNTS
+    + EM_SUMS words).  Returns the {name: device tensor} of the requested outputs: 'emb', 'logits', 'probs', 'score',
+    'pred' ([K, n, ...], model-major, each model's dad_eval_split outputs bit for bit) and 'ens_probs' [n, 4],
+    'ens_score', 'ens_pred', 'vote_pred' [n], 'votes' [n, 4] int32, 'n_correct' [n] int32 (-1 unlabelled)."""
+    prec = _PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    dev = plan.device
+    flats = _model_flats(models, plan)
+    K = len(flats)
+    w = _models_weights(weights, K)
+    out = {}
+    for name in outputs:
+        if name in _MODELS_OUTPUTS:
+            shape, dt = _MODELS_OUTPUTS[name]
+            out[name] = torch.empty((K, plan.n) + shape, dtype=dt, device=dev)
+        elif name in _MODELS_UTT_OUTPUTS:
+            shape, dt = _MODELS_UTT_OUTPUTS[name]
+            out[name] = torch.empty((plan.n,) + shape, dtype=dt, device=dev)
+        else:
+            raise ValueError("unknown output %r (one of %s)" % (name, ", ".join(list(_MODELS_OUTPUTS)
+                                                                              + list(_MODELS_UTT_OUTPUTS))))
+    fn = _lib.require("dad_eval_models", "the multi-checkpoint evaluator")
+    b = _models_buffers(plan)
+    need = int(_lib.require("dad_eval_models_workspace_bytes", "the multi-checkpoint evaluator")(
+        plan.n, plan.slabs, K, prec))
+    if b["ws"] is None or b["ws"].numel() < need:
+        b["ws"] = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    block = b["result_d"] if _block is None else _block
+    store = plan.store
+    a = _lib.DadModelsArgs()
+    a.store = store.feats.data_ptr()
+    a.rows, a.lens, a.slab_off = plan.rows_d.data_ptr(), plan.lens_d.data_ptr(), plan.slab_off_d.data_ptr()
+    a.labels = None if plan.labels_d is None else plan.labels_d.data_ptr()
+    a.n, a.slabs = plan.n, plan.slabs
+    a.store_dtype = STORE_DTYPES[store.feats.dtype]
+    a.use_entropy = int(bool(use_entropy))
+    a.precision = prec
+    for k, f in enumerate(flats):
+        a.models[k] = f.data_ptr()
+        a.weight[k] = w[k]
+    a.K = K
+    for name, t in out.items():
+        setattr(a, name, t.data_ptr() or None)
+    a.counts = block.data_ptr()
+    a.sums = block.data_ptr() + 8 * _lib.EM_COUNTS
+    _lib.check(fn(a, _lib.ptr(b["ws"]), torch.cuda.current_stream(dev).cuda_stream), "dad_eval_models")
+    b["live"] = flats              # (keeps the weights alive until the next call on this plan)
+    return out
+
+
+def _models_block(host, weights):
+    """The dict of evaluate_models_store from the host copy of the DAD_EM_* block."""
+    counts = host[:_lib.EM_COUNTS]
+    sums = host[_lib.EM_COUNTS:].view(np.float64).reshape(4, _lib.EM_MEMBERS)
+    K, M = int(counts[_lib.EM_K]), _lib.EM_MEMBERS
+    sq = lambda o: counts[o:o + M * M].reshape(M, M)[:K + 2, :K + 2].copy()
+    return {"K": K, "n": int(counts[_lib.EM_N]), "n_labelled": int(counts[_lib.EM_N_LABELLED]),
+            "n_skipped": int(counts[_lib.EM_N_SKIPPED]),
+            "nonfinite": counts[_lib.EM_NONFINITE:_lib.EM_NONFINITE + K].copy(),
+            "confusion": counts[_lib.EM_CONF:_lib.EM_CONF + 16 * M].reshape(M, 4, 4)[:K + 2].copy(),
+            "disagree": sq(_lib.EM_DISAGREE), "only": sq(_lib.EM_ONLY),
+            "hist": counts[_lib.EM_HIST:_lib.EM_HIST + K + 1].copy(),
+            "sum_score": sums[0, :K + 1].copy(), "sum_entropy": sums[1, :K + 1].copy(),
+            "sum_nll": sums[2, :K + 1].copy(), "sum_brier": sums[3, :K + 1].copy(),
+            "weights": list(weights), "block": host}
+
+
+def evaluate_models_store(models, plan_or_store, weights=None, use_entropy=True, precision="fp32", outputs=()):
+    """One dad_eval_models over the whole split and one device-to-host copy of its result block.  Members are the K
+    models, then their mean ensemble (index K), then their vote (index K + 1).  Returns {'K', 'n', 'n_labelled',
+    'n_skipped', 'nonfinite' [K], 'confusion' [K + 2, 4, 4] (row = label), 'disagree' [K + 2, K + 2] (pred_a != pred_b
+    over all n), 'only' [K + 2, K + 2] (a right and b wrong; the diagonal is a's correct count), 'hist' [K + 1]
+    (labelled utterances by how many models are right), 'sum_score', 'sum_entropy', 'sum_nll', 'sum_brier' [K + 1]
+    (float64; models, then the ensemble), 'weights', 'block'} as NumPy values, plus a device tensor per name in
+    `outputs` (enqueue_eval_models).  Raises DadError when any model has a non-finite logit."""
+    plan = EvalPlan.of(plan_or_store)
+    models = list(models)
+    out = enqueue_eval_models(models, plan, weights, use_entropy, precision, outputs)
+    K = len(models)
+    b = _models_buffers(plan)
+    b["result_h"].copy_(b["result_d"], non_blocking=True)
+    torch.cuda.current_stream(plan.device).synchronize()
+    res = _models_block(b["result_h"].numpy().copy(), _models_weights(weights, K))
+    if res["nonfinite"].any():
+        raise _lib.DadError("dad_eval_models: model(s) %s have a non-finite logit on %s of %d utterance(s) (fp16: an "
+                            "operand beyond +-65504; any precision: non-finite features)"
+                            % (np.nonzero(res["nonfinite"])[0].tolist(),
+                               res["nonfinite"][res["nonfinite"] > 0].tolist(), res["n"]))
+    res.update(out)
+    return res
+
+
+def mcnemar_exact(b, c):
+    """The exact two-sided binomial p-value of McNemar's test for the discordant counts b and c: the probability,
+    under Binomial(b + c, 1/2), of a split at least as uneven, min(1, 2 P[X <= min(b, c)]); 1.0 when b + c = 0."""
+    b, c = int(b), int(c)
+    n, k = b + c, min(b, c)
+    if n == 0:
+        return 1.0
+    tail = sum(math.comb(n, i) for i in range(k + 1))
+    return min(1.0, 2 * tail / (1 << n))          # (exact integers; the quotient is rounded once)
+
+
+def ensemble_from_block(res):
+    """ensemble_report's dict from evaluate_models_store's (every value a Python or NumPy host value)."""
+    K, n, nl = res["K"], res["n"], res["n_labelled"]
+    names = ["model_%d" % k for k in range(K)] + ["ensemble", "vote"]
+    w = np.asarray(res["weights"], np.float64)
+    wn = (w / w.sum()).astype(np.float32).astype(np.float64)
+    members = []
+    for m, name in enumerate(names):
+        d = {"name": name}
+        if nl:
+            d.update(metrics_from_confusion(res["confusion"][m]))
+        if m <= K:
+            d["mean_score"] = res["sum_score"][m] / n
+            d["mean_entropy"] = res["sum_entropy"][m] / n
+            if nl:
+                d["nll"] = res["sum_nll"][m] / nl
+                d["brier"] = res["sum_brier"][m] / nl
+        members.append(d)
+    pairs = []
+    for a in range(K + 2):
+        for b in range(a + 1, K + 2):
+            pb, pc = int(res["only"][a, b]), int(res["only"][b, a])
+            pairs.append({"a": names[a], "b": names[b], "disagreement_rate": res["disagree"][a, b] / n,
+                          "mcnemar_b": pb, "mcnemar_c": pc, "p_value": mcnemar_exact(pb, pc)})
+    rep = {"members": members, "pairs": pairs, "hist": res["hist"].tolist(),
+           "diversity": float(res["sum_entropy"][K] / n - np.dot(wn, res["sum_entropy"][:K]) / n),
+           "n": n, "n_labelled": nl, "K": K}
+    if nl:
+        rep["oracle_accuracy"] = float(res["hist"][1:].sum() / nl) * 100
+        rep["best_single"] = max(range(K), key=lambda k: members[k]["weighted_accuracy"])
+    return rep
+
+
+def ensemble_report(models, store_or_loader, weights=None, precision="fp32"):
+    """K networks compared on one split from one dad_eval_models: {'members': per member ('model_k', 'ensemble',
+    'vote') metrics_from_confusion's dict plus 'mean_score', 'mean_entropy', 'nll' (mean -ln p_y) and 'brier' (the
+    vote has no probabilities); 'pairs': per pair a < b the 'disagreement_rate', McNemar's 'mcnemar_b' (a right, b
+    wrong) and 'mcnemar_c', and the exact two-sided binomial 'p_value'; 'oracle_accuracy' (per cent of labelled
+    utterances that at least one model gets right); 'hist' (labelled utterances by how many models are right);
+    'diversity' (mean H(ensemble) - sum_k w^_k mean H(p_k) in nats, the generalised Jensen-Shannon divergence of the
+    models' predictions); 'best_single' (the model with the highest weighted accuracy)}."""
+    return ensemble_from_block(evaluate_models_store(models, store_or_loader, weights, True, precision))
