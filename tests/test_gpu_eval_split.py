@@ -12,6 +12,7 @@ import torch
 import dadpkg
 import gpu_harness as gh
 from oracle import data_oracle as do
+from split_scale import block_from_outputs as _block_from_outputs
 from test_data_cpu import _golden
 
 pytestmark = pytest.mark.gpu
@@ -99,27 +100,6 @@ def _decided(ref, min_gap):
     ok = ref["gap"] > min_gap
     assert (~ok).mean() <= 0.05, "the reference itself has %d of %d near-ties" % ((~ok).sum(), len(ok))
     return torch.from_numpy(ok)
-
-
-def _block_from_outputs(res, labels, with_teacher):
-    """The result block restated in NumPy from the kernel's own per-utterance outputs."""
-    pred = res["pred"].cpu().numpy()
-    score = res["score"].cpu().numpy()
-    valid = (labels >= 0) & (labels < 4)
-    cs = np.zeros((4, 4), np.int64)
-    np.add.at(cs, (labels[valid], pred[valid]), 1)
-    ct = np.zeros((4, 4), np.int64)
-    dis = 0
-    if with_teacher:
-        tp = res["t_pred"].cpu().numpy()
-        np.add.at(ct, (labels[valid], tp[valid]), 1)
-        dis = int((pred != tp).sum())
-    mom = np.zeros((4, 3))
-    for c in range(4):
-        v = score[labels == c].astype(np.float64)
-        if len(v):
-            mom[c] = [len(v), np.mean(v), np.std(v) ** 2]
-    return cs, ct, dis, int(valid.sum()), int((~valid).sum()), mom
 
 
 def _check_block(res, labels, with_teacher):
